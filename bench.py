@@ -7,15 +7,22 @@ resident in HBM; outputs stay in HBM. Pairs shard across ranks (one process
 per GPU, launched by torch.distributed.run); there is no collective on the data
 path -- only the barrier and the max-over-ranks timing reduction.
 
-Prints ONE JSON line on rank 0 (contract in the task statement); extra fields:
+Prints ONE JSON line on rank 0 (contract in the task statement). A plain run
+sets up, warms up, times the K steps, writes the last step's flows if
+--dump-outputs is given and prints the line; the measurements beside the
+headline figure take runs of their own and are made only with --full (their
+fields are null in a plain run):
 `roofline` for the dominant kernel (the finest-level patch-search launch,
 k_search8, ~60% of the step), which is bound by VALU issue -- its f32
 arithmetic must stay separately rounded (no FMA) to match the reference bit for
 bit -- with its HBM figures alongside; `cpu_baseline` (the C oracle in one
-process per host core, <= 16, plus a one-core sample) and `max_epe_vs_oracle`.
+process per host core, <= 16, plus a one-core sample), `max_epe_vs_oracle`,
+`tolerance_mode`, `pipelined`, `hbm_measured_peak`, `box_state` and, for N > 1,
+the rank-0 `gather`.
 """
 import argparse
 import concurrent.futures as cf
+import contextlib
 import json
 import os
 import sys
@@ -48,6 +55,13 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--preset", default="medium", choices=[p.name.lower() for p in disflow.Preset])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline figure: CPU baseline, roofline pass, HBM "
+                         "peaks, two batches in flight, tolerance mode, clock/power samples, the N > 1 gather and "
+                         "the parity spot check (the --no-* switches below drop single ones of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's flows to DIR as float32 .npy files: "
+                         "pair 0 whole and a fixed seeded sample of pixels over all pairs")
     ap.add_argument("--streams", type=int, default=0, help="sub-batch streams per step (0 = library default)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline sample budget")
     ap.add_argument("--cpu-workers", type=int, default=0, help="CPU-baseline host processes (0 = all, <= 16)")
@@ -77,6 +91,35 @@ def make_pairs(seeds, W, H):
     with cf.ThreadPoolExecutor(max_workers=min(16, len(seeds))) as ex:
         res = list(ex.map(one, seeds))
     return np.stack([a for a, _ in res]), np.stack([b for _, b in res])
+
+
+DUMP_SAMPLE_PIXELS = 1 << 22  # (x, y) flow vectors in the sample: 32 MiB as float32
+DUMP_SAMPLE_SEED = 20240517
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the flows `out` (B, H, W, 2 float32 on the device) that
+    the last timed step wrote, as float32 .npy files in `path`: pair 0 whole
+    (`flow_pair0`), and the flow vectors at DUMP_SAMPLE_PIXELS pixel positions
+    drawn once, with a fixed seed, from all B x H x W (`flow_sample`; every
+    pixel if there are no more). Inputs and positions depend only on the
+    arguments, so two builds can be compared file by file. Ranks other than 0
+    add `_rank<r>` to the names. Returns what was written, for the line."""
+    os.makedirs(path, exist_ok=True)
+    flat = out.view(-1, 2)
+    n = flat.shape[0]
+    if n > DUMP_SAMPLE_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_SAMPLE_PIXELS, replace=False))
+        sample = flat[torch.from_numpy(idx).to(out.device)]
+    else:
+        sample = flat
+    sfx = f"_rank{rank}" if rank else ""
+    files = {}
+    for name, t in (("flow_pair0" + sfx, out[0]), ("flow_sample" + sfx, sample)):
+        arr = np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(path, name + ".npy"), arr)
+        files[name + ".npy"] = {"shape": list(arr.shape), "dtype": "float32"}
+    return {"dir": path, "files": files, "sample_seed": DUMP_SAMPLE_SEED, "sample_of_pixels": n}
 
 
 CPU_WORKER_CAP = 16  # the GPU box's CPU share per GPU (gpurun: 16); nproc shows the whole host
@@ -322,7 +365,7 @@ def main():
     W, H, B = a.width, a.height, a.batch
     params = disflow.preset_params(disflow.Preset[a.preset.upper()], W, H)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:  # before any GPU call (plain forks)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:  # before any GPU call (plain forks)
         affinity = len(os.sched_getaffinity(0))
         workers = a.cpu_workers or min(CPU_WORKER_CAP, affinity)
         c = cpu_baseline(params, W, H, a.cpu_seconds, workers)
@@ -354,9 +397,14 @@ def main():
     dev = torch.device("cuda", local)
     # read-only sclk / socket-power samples of this rank's GPU (amdgpu hwmon)
     # during the timed region and the roofline pass: a VALU-bound kernel's time
-    # follows the clock, which follows the power cap
-    from disflow import boxstate
-    sampler = boxstate.Sampler(boxstate.torch_hwmon_dir(local))
+    # follows the clock, which follows the power cap; --full only
+    sampler = None
+    if a.full:
+        from disflow import boxstate
+        sampler = boxstate.Sampler(boxstate.torch_hwmon_dir(local))
+
+    def phase(name):
+        return sampler.phase(name) if sampler is not None else contextlib.nullcontext()
     if world > 1:
         import torch.distributed as dist
         if a.dist_backend == "nccl":
@@ -403,7 +451,7 @@ def main():
 
     barrier()
     torch.cuda.synchronize(dev)
-    with sampler.phase("timed"):
+    with phase("timed"):
         t0 = time.perf_counter()
         for _ in range(a.steps):
             step()
@@ -411,15 +459,17 @@ def main():
         barrier()
         el = time.perf_counter() - t0
 
+    dumped = dump_outputs(a.dump_outputs, out, rank, world) if a.dump_outputs else None
+
     # roofline pass (after the timed region): the same steps with the batch on
     # one stream, so the finest-level search launch runs without co-running
     # sub-batches; HIP dispatch events time every launch of it
     n_f, ms_f = 0, 0.0
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         eng.set_concurrency(1)
         step()
         eng.set_kernel_timing(True)  # (re)enabling starts a fresh measurement
-        with sampler.phase("roofline"):
+        with phase("roofline"):
             for _ in range(max(10, a.steps // 5)):
                 step()
             torch.cuda.synchronize(dev)
@@ -429,7 +479,7 @@ def main():
     # measured HBM peaks on this card (SURVEY 8d asks for a stream-copy peak
     # beside the 8 TB/s spec): device-to-device copy and fill of 1 GiB, events
     hbm_meas = None
-    if rank == 0:
+    if a.full and rank == 0:
         nbytes = 1 << 30
         x = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
@@ -457,7 +507,7 @@ def main():
     # batch at a time on one stream). (Linking the two contexts with
     # dis_pipeline_link forces eager enqueue: measured slower)
     piped = None
-    if not a.no_pipelined:
+    if a.full and not a.no_pipelined:
         engs = [eng, disflow.DenseInverseSearch(params, W, H, max_batch=B, device=local)]
         strs = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]  # not the default stream (implicit syncs)
         out2 = torch.empty_like(out)
@@ -501,7 +551,7 @@ def main():
     # with dispatch events, and pair 0 against the oracle; reported in its own
     # sub-object -- `value` is always the bit-exact default path
     tol = None
-    if not a.no_tolerance_mode:
+    if a.full and not a.no_tolerance_mode:
         eng.set_precision(disflow.PRECISION_FMA)
         for _ in range(max(2, a.warmup // 2)):
             step()
@@ -552,14 +602,14 @@ def main():
     # the path's one collective, outside the timed region: the
     # last step's flows of every rank gathered to rank 0 over RCCL/xGMI
     gather = None
-    if world > 1:
+    if a.full and world > 1:
         barrier()
         torch.cuda.synchronize(dev)
         gather = gather_and_verify(out, B, rank, world, a.dist_backend, sync=lambda: torch.cuda.synchronize(dev))
 
     # parity spot check on rank 0: pair 0 of the last step vs the C oracle
     max_epe = None
-    if rank == 0:
+    if a.full and rank == 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_binding
         exp = oracle_binding.calc_from_params(I0[0], I1[0], params)
@@ -589,11 +639,14 @@ def main():
         except Exception:
             traffic = None
 
-    sampler.close()
-    box = {"hwmon": sampler.dir, "timed": sampler.summary("timed"), "roofline_pass": sampler.summary("roofline"),
-           "note": "rank 0's GPU: sclk (hwmon freq1_input) and socket power (power1_input) sampled every ~2 ms, "
-                   "read-only; the quoted peaks assume 2400 MHz"}
-    clock = (box["roofline_pass"] or {}).get("sclk_MHz_mean")
+    box, clock = None, None
+    if sampler is not None:
+        sampler.close()
+        box = {"hwmon": sampler.dir, "timed": sampler.summary("timed"),
+               "roofline_pass": sampler.summary("roofline"),
+               "note": "rank 0's GPU: sclk (hwmon freq1_input) and socket power (power1_input) sampled every "
+                       "~2 ms, read-only; the quoted peaks assume 2400 MHz"}
+        clock = (box["roofline_pass"] or {}).get("sclk_MHz_mean")
     if rank == 0:
         pairs = world * B * a.steps
         line = {
@@ -617,6 +670,8 @@ def main():
                        "knobs": {"C": params.coarsest_scale, "F": params.finest_scale, "ps": params.patch_size,
                                  "it": params.iterations, "overlap": params.patch_overlap, "steps": wl["steps"]},
                        "parallelism": f"pairs sharded over {world} rank(s), no data-path collective"},
+            "full": a.full,
+            "outputs": dumped,
             "roofline": {"bound": "valu", "kernel": "k_search8, finest-level launch (patch inverse search)",
                          "achieved": achieved, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": (achieved / VALU_PEAK_TFLOPS) if achieved else None, "traffic": traffic,
@@ -643,6 +698,8 @@ def main():
             "tolerance_mode": tol,
             "pipelined": piped,
         }
+        if not a.full:  # no roofline pass was run
+            line["roofline"] = None
         print(json.dumps(line), flush=True)
     eng.close()
     if world > 1:

@@ -8,7 +8,7 @@
 #   abspawn=<lib>,<lib>,...      the same, one process per variant and round (4 rounds)
 #   levels=<lib>,<lib>,...       per-kernel one-stream durations (rocprof kernel trace)
 #   pmc=<lib>                    SQ counters of the top kernels (tools/gpu/pmc_sq.sh; CTRS= to override)
-#   bench                        bench.py default line
+#   bench                        bench.py --full line (headline and everything beside it)
 #   smoke                        __graft_entry__.smoke()
 #   tool=<name> [args]           a built tools/ binary (e.g. tool=issue_mix)
 #   py=<script> [args]           a python script of the repo (e.g. py="tools/bench_configs.py --configs colour")
@@ -35,7 +35,7 @@ for s in "$@"; do
     abspawn) run s${n}_abspawn 900 python3 tools/ab.py --spawn 4 --rounds 3 --steps 10 $(libs "$v") ;;
     levels) run s${n}_levels 600 bash tools/gpu/levels.sh $(libs "$v") ;;
     pmc) run s${n}_pmc 300 bash tools/gpu/pmc_sq.sh $(libs "$v") ;;
-    bench) run s${n}_bench 400 python bench.py ;;
+    bench) run s${n}_bench 400 python bench.py --full ;;
     smoke) run s${n}_smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tool) run s${n}_$(echo "$v" | cut -d' ' -f1) 300 ./tools/$v ;;
     py) run s${n}_$(basename "$(echo "$v" | cut -d' ' -f1)" .py) 600 python3 $v ;;

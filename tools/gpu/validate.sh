@@ -13,4 +13,4 @@ step() {  # step <name> <timeout> <cmd...>
 echo "host cores: $(nproc)"; lscpu | grep "Model name"
 step pytest_gpu 900 python -m pytest tests -m gpu -q -rf
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python bench.py --steps 5 --warmup 2 --cpu-seconds 5
+step bench 400 python bench.py --full --steps 5 --warmup 2 --cpu-seconds 5
