@@ -2,7 +2,9 @@
 // C-ABI (include/dis_abi.h).
 //
 //   dis::DenseInverseSearch   calc(I0, I1, flow) for u8 frames; presets
-//                             (the per-pair body of src/main.cpp:135-198)
+//                             (the per-pair body of src/main.cpp:135-198);
+//                             calc(I0, I1, flow_fw, flow_bw) for both directions
+//   dis::flowConsistency      forward-backward consistency mask of two fields
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -102,6 +104,19 @@ public:
     {
         check(dis_calc_batch_u8(ctx_, n, I0, I1, stride, pair_stride, flow, where, stream));
     }
+    // Both directions in one call (dis_calc_bidir_batch_u8): flow_fw is what
+    // calc(I0, I1, .) gives, flow_bw what calc(I1, I0, .) gives, bit for bit;
+    // each frame's pyramid is built once.
+    void calc(const uint8_t* I0, const uint8_t* I1, float* flow_fw, float* flow_bw, size_t stride = 0)
+    {
+        check(dis_calc_bidir_batch_u8(ctx_, 1, I0, I1, stride, 0, flow_fw, flow_bw, DIS_MEM_HOST, nullptr));
+    }
+    void calc_bidir_batch(int n, const uint8_t* I0, const uint8_t* I1, float* flow_fw, float* flow_bw,
+                          dis_mem where = DIS_MEM_HOST, void* stream = nullptr, size_t stride = 0,
+                          size_t pair_stride = 0)
+    {
+        check(dis_calc_bidir_batch_u8(ctx_, n, I0, I1, stride, pair_stride, flow_fw, flow_bw, where, stream));
+    }
     void set_concurrency(int streams) { check(dis_set_concurrency(ctx_, streams)); }
     // DIS_PRECISION_EXACT (default) or DIS_PRECISION_FMA (dis_abi.h)
     void set_precision(int mode) { check(dis_set_precision(ctx_, mode)); }
@@ -126,6 +141,17 @@ inline void flow_color(const float* flow, int n, int width, int height, uint8_t*
                        dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
 {
     check(dis_flow_color(flow, n, width, height, maxmotion, bgr, where, stream, device));
+}
+
+// Forward-backward consistency (dis_flow_consistency) of n W x H (u,v) fields,
+// on the GPU: mask 255 where fw and the backward vector sampled at its target
+// cancel within alpha1 * (|fw|^2 + |bw|^2) + alpha2; err (optional) the squared
+// round-trip distance.
+inline void flowConsistency(const float* fw, const float* bw, int n, int width, int height, uint8_t* mask,
+                            float* err = nullptr, float alpha1 = 0.01f, float alpha2 = 0.5f,
+                            dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_consistency(fw, bw, n, width, height, alpha1, alpha2, mask, err, where, stream, device));
 }
 
 // Middlebury .flo files (src/IO_flow.cpp ReadFlowFile / SaveFlowFile).

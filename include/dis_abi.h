@@ -121,6 +121,23 @@ dis_status dis_calc_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const uint8
                              size_t stride, size_t pair_stride, float* flow,
                              dis_mem where, void* stream);
 
+/* Both directions of n pairs in one call (added within ABI v8: purely
+ * additive, DIS_ABI_VERSION unchanged, no v8 caller breaks): flow_fw[k] is
+ * what dis_calc_batch_u8(I0, I1) gives for pair k, flow_bw[k] what
+ * dis_calc_batch_u8(I1, I0) gives -- bit for bit in DIS_PRECISION_EXACT, and
+ * bit for bit in DIS_PRECISION_FMA for the same n and concurrency. Each frame
+ * is read and its pyramid built once; the backward pass is the same level loop
+ * with the two frames' planes swapped. The two n*W*H*2-float outputs must not
+ * overlap. Always enqueued eagerly (never a replayed graph). DIS_MEM_HOST is
+ * synchronous and stages through device buffers for max_batch pairs that the
+ * context allocates on the first such call (DIS_ERR_OUT_OF_MEMORY if that
+ * fails); the chunked host pipeline below is not used. After this call
+ * DIS_STAGE_FALLBACK and the debug dumps describe the backward pass (DX0 / DY0
+ * are then the second frame's gradients). */
+dis_status dis_calc_bidir_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const uint8_t* I1,
+                                   size_t stride, size_t pair_stride,
+                                   float* flow_fw, float* flow_bw, dis_mem where, void* stream);
+
 /* Host-frame path (ABI v8): with DIS_MEM_HOST a batch runs in chunks of
  * chunk_pairs pairs (0 = auto, the default: about 64 MB of flow per chunk)
  * through two device slots; chunk j+1's upload, chunk j's computation and
@@ -265,6 +282,20 @@ dis_status dis_kernel_time(dis_ctx* ctx, int kernel, int* launches, double* tota
  * asynchronous on `stream`. Runs on HIP device `device`. */
 dis_status dis_flow_color(const float* flow, int n, int width, int height, float maxmotion, uint8_t* bgr,
                           dis_mem where, void* stream, int device);
+
+/* Forward-backward consistency of n W x H (u,v) fields (added within ABI v8,
+ * additive; no context, like dis_flow_color; no reference counterpart). With
+ * fw(x,y) = (u,v) and s = bw sampled bilinearly at (x+u, y+v):
+ *   err  = |fw + s|^2,  mask = err <= alpha1 * (|fw|^2 + |s|^2) + alpha2 ? 255 : 0;
+ * a target outside [0,W-1] x [0,H-1] or a NaN vector gives mask 0, err +inf.
+ * Every operation is a separately rounded f32 one (DESIGN.md "Bidirectional
+ * flow"). alpha1, alpha2 finite and >= 0 (the literature's 0.01 and 0.5 are
+ * the bindings' defaults); mask n*W*H bytes; err n*W*H floats or NULL. Device
+ * pointers: fw and bw 8-byte aligned, asynchronous on `stream`; host pointers:
+ * synchronous. bw's mask is the same call with the two fields swapped. */
+dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int width, int height,
+                                float alpha1, float alpha2, uint8_t* mask, float* err /* may be NULL */,
+                                dis_mem where, void* stream, int device);
 
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,

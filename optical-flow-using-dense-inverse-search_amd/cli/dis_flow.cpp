@@ -1,7 +1,7 @@
 // dis_flow -- frame-sequence CLI over the MI355X engine,
 // the reference's main() (src/main.cpp:59-206) with its argument conventions:
 //
-//   dis_flow                                   alley_1 frames 1..50, defaults
+//   dis_flow                                   alley_1 frames 1..50, defaults (the usage, if ./alley_1 is absent)
 //   dis_flow folder start end
 //   dis_flow folder start end iters patch_size coarsest finest overlap norm draw_grid
 //
@@ -10,7 +10,12 @@
 // commented out at src/main.cpp:137-146), --batch N (pairs per GPU call,
 // default 8; the reference is one pair at a time), --device D, --paper (the DIS
 // paper's residual and densification; not the reference's),
-// --refine K (K fixed-point iterations of variational refinement, 8f row 1).
+// --refine K (K fixed-point iterations of variational refinement, 8f row 1),
+// --bidir (both directions in one GPU call: also writes the backward flow's
+// colour coding OF_<folder>/frame_NNNN_bw.png -- and frame_NNNN_bw.flo with
+// --flo -- and the forward flow's forward-backward consistency mask as the
+// 8-bit grey frame_NNNN_mask.png, 255 = consistent), --fb-alpha A1 A2 (the
+// check's constants, default 0.01 0.5).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -47,7 +52,7 @@ void usage()
                  "3. Add full settings\n"
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
-                 "options: --flo  --batch N  --device D  --paper  --refine K"
+                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2"
               << std::endl;
 }
 
@@ -69,6 +74,8 @@ int main(int argc, char** argv)
     int draw_grid = 0;
     bool write_flo = false;
     int batch = 8, device = 0;
+    bool bidir = false;
+    float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -79,6 +86,11 @@ int main(int argc, char** argv)
             batch = std::atoi(argv[++i]);
         } else if (a == "--device" && i + 1 < argc) {
             device = std::atoi(argv[++i]);
+        } else if (a == "--bidir") {
+            bidir = true;
+        } else if (a == "--fb-alpha" && i + 2 < argc) {
+            fb_alpha1 = (float)std::atof(argv[++i]);
+            fb_alpha2 = (float)std::atof(argv[++i]);
         } else if (a == "--paper") {
             p.paper_mode = 1;
         } else if (a == "--refine" && i + 1 < argc) {
@@ -109,6 +121,11 @@ int main(int argc, char** argv)
         return 2;
     }
     if (batch < 1) batch = 1;
+    struct stat sb;
+    if (argc == 1 && ::stat(folder.c_str(), &sb) != 0) {  // no arguments and no default sequence here
+        usage();
+        return 0;
+    }
     const std::string out_dir = "OF_" + folder;
     ::mkdir(out_dir.c_str(), 0755);  // CreateFolder (src/main.cpp:52-57): existing is fine
 
@@ -135,7 +152,19 @@ int main(int argc, char** argv)
                 std::copy(frames[k + 1].px.begin(), frames[k + 1].px.end(), I1.begin() + (size_t)k * W * H);
             }
             std::vector<float> flow((size_t)n * W * H * 2);
-            eng->calc_batch(n, I0.data(), I1.data(), flow.data());
+            std::vector<float> flow_bw;
+            std::vector<uint8_t> mask, bgr_bw;
+            if (bidir) {
+                flow_bw.resize(flow.size());
+                mask.resize((size_t)n * W * H);
+                bgr_bw.resize((size_t)n * W * H * 3);
+                eng->calc_bidir_batch(n, I0.data(), I1.data(), flow.data(), flow_bw.data());
+                dis::flowConsistency(flow.data(), flow_bw.data(), n, W, H, mask.data(), nullptr, fb_alpha1, fb_alpha2,
+                                     DIS_MEM_HOST, nullptr, device);
+                dis::check(dis_flow_color(flow_bw.data(), n, W, H, -1.0f, bgr_bw.data(), DIS_MEM_HOST, nullptr, device));
+            } else {
+                eng->calc_batch(n, I0.data(), I1.data(), flow.data());
+            }
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             for (int k = 0; k < n; ++k) {
@@ -143,6 +172,13 @@ int main(int argc, char** argv)
                 png::write_bgr(base + ".png", bgr.data() + (size_t)k * W * H * 3, W, H);
                 if (write_flo)
                     dis::check(dis_write_flo((base + ".flo").c_str(), flow.data() + (size_t)k * W * H * 2, W, H, 2));
+                if (bidir) {
+                    png::write_bgr(base + "_bw.png", bgr_bw.data() + (size_t)k * W * H * 3, W, H);
+                    png::write_gray(base + "_mask.png", mask.data() + (size_t)k * W * H, W, H);
+                    if (write_flo)
+                        dis::check(dis_write_flo((base + "_bw.flo").c_str(), flow_bw.data() + (size_t)k * W * H * 2, W,
+                                                 H, 2));
+                }
                 std::cout << "finish " << frame_name(folder, i0 + k) << ".png" << std::endl;
             }
         }

@@ -8,7 +8,7 @@
 // point Rec.601 luma (R*4899 + G*9617 + B*1868 + 2^13) >> 14, alpha dropped.
 // (OpenCV is absent here, so that conversion is unpinned; gray PNGs, the
 // usual optical-flow benchmark input after conversion, are exact.)
-// Encode: 8-bit RGB, filter 0, zlib level 6.
+// Encode: 8-bit RGB or grey, filter 0, zlib level 6.
 #pragma once
 
 #include <zlib.h>
@@ -170,21 +170,11 @@ inline Gray decode_gray(const std::vector<uint8_t>& d, const std::string& name =
 
 inline Gray read_gray(const std::string& path) { return decode_gray(detail::read_file(path), path); }
 
-// 8-bit RGB PNG from BGR pixels (OpenCV Vec3b order, as cv::imwrite takes them)
-inline std::vector<uint8_t> encode_bgr(const uint8_t* bgr, int w, int h)
+// One 8-bit image of the given colour type (0 grey, 2 RGB) from filter-0
+// scanlines (a 0 byte, then the row's samples), zlib level 6
+inline std::vector<uint8_t> encode_rows(const std::vector<uint8_t>& raw, int w, int h, uint8_t colour_type)
 {
     using namespace detail;
-    std::vector<uint8_t> raw((size_t)(3 * w + 1) * h);
-    for (int y = 0; y < h; ++y) {
-        uint8_t* o = &raw[(size_t)y * (3 * w + 1)];
-        o[0] = 0;
-        for (int x = 0; x < w; ++x) {
-            const uint8_t* s = bgr + ((size_t)y * w + x) * 3;
-            o[1 + 3 * x] = s[2];
-            o[2 + 3 * x] = s[1];
-            o[3 + 3 * x] = s[0];
-        }
-    }
     uLongf zlen = compressBound(raw.size());
     std::vector<uint8_t> z(zlen);
     if (compress2(z.data(), &zlen, raw.data(), raw.size(), 6) != Z_OK) throw std::runtime_error("png: compress");
@@ -200,20 +190,58 @@ inline std::vector<uint8_t> encode_bgr(const uint8_t* bgr, int w, int h)
     std::vector<uint8_t> ihdr;
     put32(ihdr, (uint32_t)w);
     put32(ihdr, (uint32_t)h);
-    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});
+    ihdr.insert(ihdr.end(), {8, colour_type, 0, 0, 0});
     chunk("IHDR", ihdr);
     chunk("IDAT", z);
     chunk("IEND", {});
     return out;
 }
 
-inline void write_bgr(const std::string& path, const uint8_t* bgr, int w, int h)
+// 8-bit RGB PNG from BGR pixels (OpenCV Vec3b order, as cv::imwrite takes them)
+inline std::vector<uint8_t> encode_bgr(const uint8_t* bgr, int w, int h)
 {
-    const std::vector<uint8_t> d = encode_bgr(bgr, w, h);
+    std::vector<uint8_t> raw((size_t)(3 * w + 1) * h);
+    for (int y = 0; y < h; ++y) {
+        uint8_t* o = &raw[(size_t)y * (3 * w + 1)];
+        o[0] = 0;
+        for (int x = 0; x < w; ++x) {
+            const uint8_t* s = bgr + ((size_t)y * w + x) * 3;
+            o[1 + 3 * x] = s[2];
+            o[2 + 3 * x] = s[1];
+            o[3 + 3 * x] = s[0];
+        }
+    }
+    return encode_rows(raw, w, h, 2);
+}
+
+// 8-bit grey PNG (the CLI's consistency mask)
+inline std::vector<uint8_t> encode_gray(const uint8_t* px, int w, int h)
+{
+    std::vector<uint8_t> raw((size_t)(w + 1) * h);
+    for (int y = 0; y < h; ++y) {
+        uint8_t* o = &raw[(size_t)y * (w + 1)];
+        o[0] = 0;
+        for (int x = 0; x < w; ++x) o[1 + x] = px[(size_t)y * w + x];
+    }
+    return encode_rows(raw, w, h, 0);
+}
+
+inline void write_file(const std::string& path, const std::vector<uint8_t>& d)
+{
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f) throw std::runtime_error("cannot create " + path);
     const bool ok = std::fwrite(d.data(), 1, d.size(), f) == d.size();
     if (std::fclose(f) != 0 || !ok) throw std::runtime_error("write failed: " + path);
+}
+
+inline void write_bgr(const std::string& path, const uint8_t* bgr, int w, int h)
+{
+    write_file(path, encode_bgr(bgr, w, h));
+}
+
+inline void write_gray(const std::string& path, const uint8_t* px, int w, int h)
+{
+    write_file(path, encode_gray(px, w, h));
 }
 
 }  // namespace png

@@ -166,6 +166,13 @@ hipError_t launch_flow_color(const float* flow, int n, int W, int H, float maxmo
 // device workspace words launch_flow_color needs for n fields (zeroed by it)
 size_t flow_color_ws_words(int n);
 
+// Forward-backward consistency of n W x H (u,v) fields (dis_consistency.hip):
+// mask (u8, 255 = consistent) and, if err is non-null, the squared round-trip
+// distance per pixel. fw and bw 8-byte aligned.
+long long flow_consistency_blocks(int n, int W, int H);  // grid size of the launch
+hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int W, int H, float alpha1,
+                                   float alpha2, uint8_t* mask, float* err, hipStream_t s, Timing t = {});
+
 // Variational refinement of one level's dense flow (dis_varref.hip).
 constexpr int kVarRefPlanes = 8;   // per-pair workspace planes
 constexpr int kVarRefSor = 5;      // red-black SOR sweeps per fixed-point iteration

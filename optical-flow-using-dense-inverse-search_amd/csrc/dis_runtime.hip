@@ -257,10 +257,11 @@ struct dis_ctx {
     // variational refinement: its ~16 launches per fixed-point iteration per level
     // are replayed as one HIP graph per (sub-batch, level), captured on first use
     // (all pointers are context workspace; re-captured when the slice changes)
+    // and one per direction: a bidirectional call's backward pass swaps the frames
     struct VrGraph {
         hipGraphExec_t exec = nullptr;
         int n = -1, p0 = -1;
-    } vrg[kMaxSub][dis::kMaxLevels];
+    } vrg[2][kMaxSub][dis::kMaxLevels];
     hipStream_t cap = nullptr;  // capture-only stream
     // The whole batch call (both sub-batches' pyramid, level searches and
     // output, with the fork/join) replayed as one HIP graph: dis_set_graphs,
@@ -304,6 +305,10 @@ struct dis_ctx {
     // (0 = auto)
     std::unique_ptr<HostPipe> hp;
     int host_chunk = 0;
+    // dis_calc_bidir_batch_u8 with DIS_MEM_HOST: device staging for max_batch
+    // pairs (both frames; both flows), made on the first such call
+    uint8_t* bd_in = nullptr;
+    float2* bd_out = nullptr;
     // kernel timing
     int timing = 0;
     struct Rec {
@@ -359,6 +364,10 @@ void free_ws(dis_ctx* c)
     hipFree(c->vr_ws);
     c->vr_ws = nullptr;
     c->hp.reset();
+    hipFree(c->bd_in);
+    hipFree(c->bd_out);
+    c->bd_in = nullptr;
+    c->bd_out = nullptr;
     c->img0 = c->img1 = c->dx = c->dy = nullptr;
     c->pu = c->dense = nullptr;
 }
@@ -413,6 +422,9 @@ int upsample_xmax(const dis::Geometry& g)
 }
 
 constexpr int kStageFront = 1000, kStageBack = -1000;  // other stages: the level index
+// between the two passes of a bidirectional call: what the front stage did for
+// frame 0's role, redone for frame 1 (fallback counts, generic-path gradients)
+constexpr int kStageTurn = 2000;
 
 // roctx markers, resolved at first use with dlopen (no link-time dependency:
 // without the roctx library, or without a tool attached, they are no-ops).
@@ -446,6 +458,8 @@ struct StageRange {
             std::snprintf(b, sizeof b, "dis: pyramid sub %d", sub);
         else if (stage == kStageBack)
             std::snprintf(b, sizeof b, "dis: output sub %d", sub);
+        else if (stage == kStageTurn)
+            std::snprintf(b, sizeof b, "dis: turn sub %d", sub);
         else
             std::snprintf(b, sizeof b, "dis: level %d sub %d", stage, sub);
         if (roctx().push) roctx().push(b);
@@ -505,16 +519,19 @@ dis::DensifyArgs densify_args(const dis_ctx* c, int l, const float* img0, const 
 // front end (pyramid), one level (search, and densify + refinement when on),
 // or the back end (output). run_batches issues the stages stage-major across
 // the sub-batches, so every sub-batch's next kernels are queued early even
-// when the host is slow to enqueue a long stage.
+// when the host is slow to enqueue a long stage. dir = 1 is the backward pass
+// of a bidirectional call: the same stages with the two frames' planes
+// swapped (the pyramid builds both frames alike; everything after it reads
+// them through img0 / img1 below), after a kStageTurn stage.
 dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, const uint8_t* I1, size_t stride,
-                     size_t pair_stride, float2* flow, hipStream_t s, int stage)
+                     size_t pair_stride, float2* flow, hipStream_t s, int stage, int dir = 0)
 {
     // this sub-batch's fallback counts (one per level)
     int* const fb_count = c->fb + (size_t)sub * kFbCounters;
     const dis::Geometry& g = c->g;
     // this sub-batch's slice of the workspace (pairs p0 .. p0+n-1)
-    float* const img0 = c->img0 + (size_t)p0 * g.plane_stride;
-    float* const img1 = c->img1 + (size_t)p0 * g.plane_stride;
+    float* const img0 = (dir ? c->img1 : c->img0) + (size_t)p0 * g.plane_stride;
+    float* const img1 = (dir ? c->img0 : c->img1) + (size_t)p0 * g.plane_stride;
     float* const gdx = c->dx + (size_t)p0 * g.plane_stride;
     float* const gdy = c->dy + (size_t)p0 * g.plane_stride;
     float2* const pu = c->pu + (size_t)p0 * g.u_stride;
@@ -522,7 +539,18 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
     const bool fast = g.ps == 8 && c->variant != 1;
     const bool vr = c->p.var_refine_iters > 0;
     const bool paper = c->p.paper_mode != 0;
+    if (stage == kStageTurn) {
+        // The searches append to lists sized for one pass (blocks(level) x
+        // pairs) at a count only the front stage zeroes: the backward pass
+        // starts its lists at 0 again, in stream order after the forward
+        // pass's last search.
+        DIS_HIP(hipMemsetAsync(fb_count, 0, sizeof(int) * (g.C + 1), s));
+        if (!fast || c->debug)  // dx / dy held frame 0's gradients
+            for (int l = g.F; l <= g.C; ++l) DIS_HIP(dis::launch_sobel(g, l, img0, gdx, gdy, n, s));
+        return DIS_OK;
+    }
     if (stage == kStageFront) {
+        if (dir != 0) return fail(DIS_ERR_INTERNAL, "the front stage runs once, in the forward direction");
         if (fast && g.C >= 1) {
             dis::PyramidArgs pa{};
             pa.I0 = I0;
@@ -678,7 +706,7 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
                 DIS_HIP(dis::launch_var_refine(v, n, s, l == g.F ? +tf : nullptr, c));
                 continue;
             }
-            auto& G = c->vrg[sub][l];  // the level's launches replayed as one HIP graph
+            auto& G = c->vrg[dir ? 1 : 0][sub][l];  // the level's launches replayed as one HIP graph
             if (G.n != n || G.p0 != p0) {
                 if (G.exec) hipGraphExecDestroy(G.exec);
                 G.exec = nullptr;
@@ -759,8 +787,13 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
 // sub-batches run in lockstep (staggered starts, stream priorities and
 // uneven splits measured 1-4.5 % slower: DESIGN.md 7), stages issued
 // stage-major so every sub-batch's next kernels are queued early.
+// flow_bw non-null (dis_calc_bidir_batch_u8, never captured): after the
+// forward pass every sub-batch runs the turn stage, the levels and the back
+// end once more with the frames swapped, into flow_bw -- one pyramid, the same
+// workspace, split, fork and join.
 dis_status run_batches(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, size_t stride,
-                       size_t pair_stride, float2* flow, hipStream_t s, bool capturing = false)
+                       size_t pair_stride, float2* flow, hipStream_t s, bool capturing = false,
+                       float2* flow_bw = nullptr)
 {
     // refinement: one stream. Its many short bandwidth-bound kernels stall
     // behind a co-running sub-batch's long search launches (measured on
@@ -770,11 +803,19 @@ dis_status run_batches(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, 
     std::vector<int> stages = {kStageFront};
     for (int l = c->g.C; l >= c->g.F; --l) stages.push_back(l);
     stages.push_back(kStageBack);
+    const size_t nfw = stages.size();  // stages from here on run backward
+    if (flow_bw) {
+        if (capturing) return fail(DIS_ERR_INTERNAL, "bidirectional calls are not captured");
+        stages.push_back(kStageTurn);
+        for (int l = c->g.C; l >= c->g.F; --l) stages.push_back(l);
+        stages.push_back(kStageBack);
+    }
     if (c->needs_wait(s) && !capturing) DIS_HIP(hipStreamWaitEvent(s, c->done, 0));  // the workspace is free
     if (S <= 1) {
-        for (int st : stages) {
-            StageRange range(st, 0);
-            dis_status r = run_batch(c, 0, n, 0, I0, I1, stride, pair_stride, flow, s, st);
+        for (size_t i = 0; i < stages.size(); ++i) {
+            StageRange range(stages[i], 0);
+            const int dir = i >= nfw ? 1 : 0;
+            dis_status r = run_batch(c, 0, n, 0, I0, I1, stride, pair_stride, dir ? flow_bw : flow, s, stages[i], dir);
             if (r != DIS_OK) return r;
         }
         c->last_batch = n;
@@ -820,9 +861,11 @@ dis_status run_batches(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, 
         } else {
             const int k = o.stream - 1, st = stages[o.stage];
             const int a = (int)((long long)n * k / S), b = (int)((long long)n * (k + 1) / S);
+            const int dir = (size_t)o.stage >= nfw ? 1 : 0;
             StageRange range(st, k);
             dis_status r = run_batch(c, k, b - a, a, I0 + (size_t)a * pair_stride, I1 + (size_t)a * pair_stride,
-                                     stride, pair_stride, flow + (size_t)a * fpp, stream_of(o.stream), st);
+                                     stride, pair_stride, (dir ? flow_bw : flow) + (size_t)a * fpp,
+                                     stream_of(o.stream), st, dir);
             if (r != DIS_OK) return r;
         }
     }
@@ -1387,9 +1430,10 @@ dis_status dis_destroy(dis_ctx* c)
         if (c->join[k]) hipEventDestroy(c->join[k]);
     if (c->fork) hipEventDestroy(c->fork);
     if (c->done) hipEventDestroy(c->done);
-    for (auto& row : c->vrg)
-        for (auto& G : row)
-            if (G.exec) hipGraphExecDestroy(G.exec);
+    for (auto& d : c->vrg)
+        for (auto& row : d)
+            for (auto& G : row)
+                if (G.exec) hipGraphExecDestroy(G.exec);
     for (auto& G : c->mg) {
         if (G.exec) hipGraphExecDestroy(G.exec);
         if (G.last) hipEventDestroy(G.last);
@@ -1418,6 +1462,69 @@ dis_status dis_calc_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
     }
     if (where != DIS_MEM_HOST) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
     return calc_host(c, n, I0, I1, stride, pair_stride, flow);
+}
+
+// Both directions in one call: always the eager enqueue (never the main graph
+// cache, whose key and captured arguments know one direction only). After it,
+// DIS_STAGE_FALLBACK and the debug dumps describe the backward pass.
+dis_status dis_calc_bidir_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, size_t stride,
+                                   size_t pair_stride, float* flow_fw, float* flow_bw, dis_mem where, void* stream)
+{
+    // (what needs no context first: checked the same with or without a device)
+    if (!I0 || !I1 || !flow_fw || !flow_bw) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
+    if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    if (flow_fw == flow_bw) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (n > c->max_batch) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    const int W = c->g.W, H = c->g.H;
+    if (stride == 0) stride = (size_t)W;
+    if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
+    if (pair_stride == 0) pair_stride = stride * H;
+    if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
+    const size_t fpp = (size_t)W * H;  // float2 per pair
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(flow_fw), b0 = reinterpret_cast<uintptr_t>(flow_bw);
+    const size_t fbytes = sizeof(float2) * fpp * (size_t)n;
+    if (a0 < b0 + fbytes && b0 < a0 + fbytes)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
+    DIS_HIP(hipSetDevice(c->device));
+    if (where == DIS_MEM_DEVICE) {
+        std::lock_guard<std::mutex> lock(pool_mutex(c->device));  // eager enqueue onto the pooled streams
+        return run_batches(c, n, I0, I1, stride, pair_stride, reinterpret_cast<float2*>(flow_fw),
+                           reinterpret_cast<hipStream_t>(stream), false, reinterpret_cast<float2*>(flow_bw));
+    }
+    // host memory: synchronous, staged through device buffers for max_batch
+    // pairs made on the first such call (the chunked pipeline of
+    // dis_calc_batch_u8 is not used here)
+    const size_t B = (size_t)c->max_batch;
+    if (!c->bd_in || !c->bd_out) {
+        if ((!c->bd_in && hipMalloc(&c->bd_in, 2 * fpp * B) != hipSuccess) ||
+            (!c->bd_out && hipMalloc(&c->bd_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(DIS_ERR_OUT_OF_MEMORY, "bidirectional host-path device buffer allocation failed");
+        }
+    }
+    const hipStream_t s = c->own;
+    uint8_t* const d0 = c->bd_in;
+    uint8_t* const d1 = c->bd_in + fpp * B;
+    float2* const dfw = c->bd_out;
+    float2* const dbw = c->bd_out + fpp * B;
+    for (int k = 0; k < n; ++k) {
+        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
+        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
+    }
+    {
+        std::lock_guard<std::mutex> lock(pool_mutex(c->device));
+        dis_status st = run_batches(c, n, d0, d1, (size_t)W, fpp, dfw, s, false, dbw);
+        if (st != DIS_OK) {
+            (void)hipStreamSynchronize(s);
+            return st;
+        }
+    }
+    DIS_HIP(hipMemcpyAsync(flow_fw, dfw, fbytes, hipMemcpyDeviceToHost, s));
+    DIS_HIP(hipMemcpyAsync(flow_bw, dbw, fbytes, hipMemcpyDeviceToHost, s));
+    DIS_HIP(hipStreamSynchronize(s));
+    return DIS_OK;
 }
 
 dis_status dis_set_host_pipeline(dis_ctx* c, int chunk_pairs)
@@ -1794,6 +1901,54 @@ dis_status dis_flow_color(const float* flow, int n, int width, int height, float
     hipFree(dflow);
     hipFree(dbgr);
     hipFree(maxbits);
+    return rc;
+}
+
+dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int width, int height, float alpha1,
+                                float alpha2, uint8_t* mask, float* err, dis_mem where, void* stream, int device)
+{
+    if (!fw || !bw || !mask) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
+    // pixel coordinates are exact floats
+    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "field too large");
+    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0.0f || alpha2 < 0.0f)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "alpha1 and alpha2 must be finite and >= 0");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    if (dis::flow_consistency_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    if (where == DIS_MEM_DEVICE &&
+        (((reinterpret_cast<uintptr_t>(fw) | reinterpret_cast<uintptr_t>(bw)) & 7) || (reinterpret_cast<uintptr_t>(err) & 3)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be 8-byte aligned, err 4-byte aligned");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    DIS_HIP(hipSetDevice(device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (where == DIS_MEM_DEVICE) {
+        DIS_HIP(dis::launch_flow_consistency(fw, bw, n, width, height, alpha1, alpha2, mask, err, s));
+        return DIS_OK;
+    }
+    const size_t px = (size_t)width * height * n;
+    float *dfw = nullptr, *dbw = nullptr, *derr = nullptr;
+    uint8_t* dmask = nullptr;
+    dis_status rc = DIS_OK;
+    if (hipMalloc(&dfw, sizeof(float) * 2 * px) != hipSuccess || hipMalloc(&dbw, sizeof(float) * 2 * px) != hipSuccess ||
+        hipMalloc(&dmask, px) != hipSuccess || (err && hipMalloc(&derr, sizeof(float) * px) != hipSuccess)) {
+        (void)hipGetLastError();
+        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
+    } else if (hipMemcpyAsync(dfw, fw, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipMemcpyAsync(dbw, bw, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s) != hipSuccess ||
+               dis::launch_flow_consistency(dfw, dbw, n, width, height, alpha1, alpha2, dmask, derr, s) != hipSuccess ||
+               hipMemcpyAsync(mask, dmask, px, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               (err && hipMemcpyAsync(err, derr, sizeof(float) * px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+               hipStreamSynchronize(s) != hipSuccess) {
+        rc = fail(DIS_ERR_DEVICE, "flow consistency check failed");
+    }
+    hipFree(dfw);
+    hipFree(dbw);
+    hipFree(dmask);
+    hipFree(derr);
     return rc;
 }
 

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "dis_set_concurrency", "dis_set_precision", "dis_set_graphs", "dis_flow_color", "dis_flo_info",
     "dis_read_flo", "dis_write_flo", "dis_build_kind", "dis_set_host_pipeline", "dis_host_pipeline_info",
     "dis_host_alloc", "dis_host_free", "dis_batch_stream_plan", "dis_check_stream_plan",
+    "dis_calc_bidir_batch_u8", "dis_flow_consistency",
 )
 
 
@@ -167,6 +168,10 @@ def lib() -> ctypes.CDLL:
             L.dis_host_free.argtypes = [V]
             L.dis_batch_stream_plan.argtypes = [I, I, P(I), I, P(I)]
             L.dis_check_stream_plan.argtypes = [P(I), I, I, I]
+        if hasattr(L, "dis_calc_bidir_batch_u8"):  # (added within v8; older v8 builds load for A/B timing)
+            L.dis_calc_bidir_batch_u8.argtypes = [V, I, V, V, Z, Z, V, V, I, V]
+        if hasattr(L, "dis_flow_consistency"):
+            L.dis_flow_consistency.argtypes = [V, V, I, I, I, F, F, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -228,6 +233,38 @@ def flow_color(flow: np.ndarray, maxmotion: float = -1.0, device: int = 0) -> np
     return out[0] if single else out
 
 
+def flow_consistency(fw: np.ndarray, bw: np.ndarray, alpha1: float = 0.01, alpha2: float = 0.5,
+                     with_err: bool = False, device: int = 0):
+    """Forward-backward consistency (dis_flow_consistency) of (H, W, 2) or
+    (n, H, W, 2) float fields on the GPU -> u8 mask (..., H, W), 255 where
+    following fw and then the backward vector sampled there leads back within
+    alpha1 * (|fw|^2 + |bw|^2) + alpha2; with_err: also the squared round-trip
+    distance (float32, +inf where the target leaves the frame)."""
+    f = np.ascontiguousarray(fw, dtype=np.float32)
+    b = np.ascontiguousarray(bw, dtype=np.float32)
+    single = f.ndim == 3
+    if single:
+        f, b = f[None], (b[None] if b.ndim == 3 else b)
+    if f.ndim != 4 or f.shape[-1] != 2 or b.shape != f.shape:
+        raise DisError(DIS_ERR_INVALID_ARGUMENT, "fw and bw must both be (H, W, 2) or (n, H, W, 2)")
+    n, H, W = f.shape[:3]
+    mask = np.empty((n, H, W), np.uint8)
+    err = np.empty((n, H, W), np.float32) if with_err else None
+    _check(lib().dis_flow_consistency(_ptr(f), _ptr(b), n, W, H, float(alpha1), float(alpha2), _ptr(mask),
+                                      _ptr(err) if with_err else None, MEM_HOST, None, device))
+    if single:
+        mask, err = mask[0], (err[0] if with_err else None)
+    return (mask, err) if with_err else mask
+
+
+def flow_consistency_device(fw_ptr: int, bw_ptr: int, n: int, width: int, height: int, mask_ptr: int,
+                            err_ptr: int = 0, alpha1: float = 0.01, alpha2: float = 0.5, stream: int = 0,
+                            device: int = 0) -> None:
+    """dis_flow_consistency on raw device pointers, asynchronous on `stream`."""
+    _check(lib().dis_flow_consistency(fw_ptr, bw_ptr, n, width, height, float(alpha1), float(alpha2), mask_ptr,
+                                      err_ptr or None, MEM_DEVICE, stream or None, device))
+
+
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
     """Read a Middlebury .flo file (src/IO_flow.cpp:10-53) -> (H, W, channels) float32."""
     w, h = ctypes.c_int(), ctypes.c_int()
@@ -281,6 +318,7 @@ class DenseInverseSearch:
             params = preset_params(Preset(params), width, height)
         self.params = params
         self.width, self.height, self.max_batch = width, height, max_batch
+        self.device = device
         self._ctx = ctypes.c_void_p()
         _check(lib().dis_create(ctypes.byref(self._ctx), ctypes.byref(params._c()), width, height,
                                 max_batch, device))
@@ -316,6 +354,36 @@ class DenseInverseSearch:
         """Asynchronous calc on device-resident buffers (raw device pointers)."""
         _check(lib().dis_calc_batch_u8(self._ctx, n, I0_ptr, I1_ptr, stride, pair_stride, flow_ptr,
                                        MEM_DEVICE, stream or None))
+
+    def calc_bidir(self, I0: np.ndarray, I1: np.ndarray):
+        """u8 H x W frames (host) -> (flow I0->I1, flow I1->I0), one pyramid."""
+        fw, bw = self.calc_bidir_batch(I0[None], I1[None])
+        return fw[0], bw[0]
+
+    def calc_bidir_batch(self, I0: np.ndarray, I1: np.ndarray, consistency: bool = False,
+                         alpha1: float = 0.01, alpha2: float = 0.5):
+        """dis_calc_bidir_batch_u8 on host frames: (fw, bw), bit-equal to
+        calc_batch(I0, I1) and calc_batch(I1, I0). consistency=True also returns
+        (mask_fw, mask_bw): flow_consistency(fw, bw) and flow_consistency(bw, fw)."""
+        I0 = np.ascontiguousarray(I0, dtype=np.uint8)
+        I1 = np.ascontiguousarray(I1, dtype=np.uint8)
+        if I0.shape != I1.shape or I0.ndim != 3 or I0.shape[1:] != (self.height, self.width):
+            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"frames must be (n, {self.height}, {self.width})")
+        n = I0.shape[0]
+        fw = np.empty((n, self.height, self.width, 2), np.float32)
+        bw = np.empty((n, self.height, self.width, 2), np.float32)
+        _check(lib().dis_calc_bidir_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
+                                             self.width * self.height, _ptr(fw), _ptr(bw), MEM_HOST, None))
+        if not consistency:
+            return fw, bw
+        return (fw, bw, flow_consistency(fw, bw, alpha1, alpha2, device=self.device),
+                flow_consistency(bw, fw, alpha1, alpha2, device=self.device))
+
+    def calc_bidir_device(self, n: int, I0_ptr: int, I1_ptr: int, fw_ptr: int, bw_ptr: int, stream: int = 0,
+                          stride: int = 0, pair_stride: int = 0) -> None:
+        """Asynchronous bidirectional calc on device-resident buffers (raw device pointers)."""
+        _check(lib().dis_calc_bidir_batch_u8(self._ctx, n, I0_ptr, I1_ptr, stride, pair_stride, fw_ptr, bw_ptr,
+                                             MEM_DEVICE, stream or None))
 
     def set_host_pipeline(self, chunk_pairs: int = 0) -> None:
         """dis_set_host_pipeline: pairs per chunk of a host-memory batch call
