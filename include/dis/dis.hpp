@@ -35,6 +35,9 @@ enum class Preset {
     REFERENCE = DIS_PRESET_REFERENCE,
 };
 
+// the two forms of a warm start's `init` argument (dis_init_kind)
+enum class InitKind { COARSE = DIS_INIT_COARSE, FULLRES = DIS_INIT_FULLRES };
+
 class Error : public std::runtime_error {
 public:
     Error(dis_status s, const std::string& what) : std::runtime_error(what), status_(s) {}
@@ -116,6 +119,36 @@ public:
                           size_t pair_stride = 0)
     {
         check(dis_calc_bidir_batch_u8(ctx_, n, I0, I1, stride, pair_stride, flow_fw, flow_bw, where, stream));
+    }
+    // Warm start (dis_calc_batch_init_u8): the coarsest level starts from
+    // `init` -- a full-resolution W*H*2 flow such as the previous pair's result
+    // (InitKind::FULLRES; it may be `flow` itself) or an init plane of
+    // initPlaneSize() vectors (InitKind::COARSE). init == nullptr is the plain
+    // calc.
+    void calc(const uint8_t* I0, const uint8_t* I1, float* flow, const float* init, InitKind kind, size_t stride = 0)
+    {
+        check(dis_calc_batch_init_u8(ctx_, 1, I0, I1, stride, 0, init, static_cast<int>(kind), flow, DIS_MEM_HOST,
+                                     nullptr));
+    }
+    void calc_batch_init(int n, const uint8_t* I0, const uint8_t* I1, const float* init, InitKind kind, float* flow,
+                         dis_mem where = DIS_MEM_HOST, void* stream = nullptr, size_t stride = 0,
+                         size_t pair_stride = 0)
+    {
+        check(dis_calc_batch_init_u8(ctx_, n, I0, I1, stride, pair_stride, init, static_cast<int>(kind), flow, where,
+                                     stream));
+    }
+    // (iw, ih) of one pair's init plane
+    std::pair<int, int> initPlaneSize() const
+    {
+        int iw = 0, ih = 0;
+        check(dis_init_plane_size(ctx_, &iw, &ih));
+        return {iw, ih};
+    }
+    // the reduction alone: n full-resolution flows -> n init planes
+    void flow_to_init(int n, const float* flow, float* init_planes, dis_mem where = DIS_MEM_HOST,
+                      void* stream = nullptr)
+    {
+        check(dis_flow_to_init(ctx_, n, flow, init_planes, where, stream));
     }
     void set_concurrency(int streams) { check(dis_set_concurrency(ctx_, streams)); }
     // DIS_PRECISION_EXACT (default) or DIS_PRECISION_FMA (dis_abi.h)

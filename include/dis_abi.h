@@ -138,6 +138,54 @@ dis_status dis_calc_bidir_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const
                                    size_t stride, size_t pair_stride,
                                    float* flow_fw, float* flow_bw, dis_mem where, void* stream);
 
+/* Temporal warm start (added within ABI v8: purely additive, DIS_ABI_VERSION
+ * unchanged; the reference always starts from zero, src/patch_grid.cpp:45,80;
+ * OpenCV's DIS takes an in/out flow the same way). A warm-started call behaves
+ * as if a level C+1 had produced a dense flow: a coarsest-level patch with
+ * reference pixel (rx, ry) starts at 2 * I[ry >> 1][rx >> 1], exactly as every
+ * finer level starts from the level above it. I is the pair's init plane:
+ * iw x ih = (W_C + 1) / 2 x (H_C + 1) / 2 float2 (u, v), row stride iw, in
+ * level-(C+1) pixels, W_C x H_C the padded frame's level-C size
+ * (dis_init_plane_size). `init` comes in one of two forms:
+ *   DIS_INIT_COARSE:  n such planes, pair stride iw * ih float2;
+ *   DIS_INIT_FULLRES: n W x H x 2 flows in full-resolution pixels, the layout
+ *     dis_calc_batch_u8 writes (a previous call's output is a valid argument).
+ *     The engine extends each to the padded frame (replicate) and halves it
+ *     C+1 times, P_{j+1}(x, y) = ((a + b) + (c + d)) * 0.125f over the 2 x 2
+ *     block a b / c d of P_j, every f32 operation separately rounded; only the
+ *     last step can meet an odd size, and clamps its source indices.
+ * In both forms the search reads a context-owned plane, never the caller's
+ * memory: the kernel that fills it replaces every input component that is not
+ * finite or has |c| >= 1e9 by 0 (dis_flow_color's notion of an invalid
+ * vector). Finite starts of any size are safe: a start outside the level's
+ * valid region is rejected by the search and the patch keeps its init.
+ *
+ * init == NULL is dis_calc_batch_u8, bit for bit; an all-zero plane gives the
+ * same flow. Works with every kernel variant, patch size, paper_mode,
+ * var_refine_iters, both precisions and any concurrency. `init` may be the
+ * very buffer `flow` points to (flow in, flow out): the plane is filled on the
+ * call's stream before the level chain is enqueued on it (and on streams
+ * forked from it), so stream order completes the plane before any output is
+ * written. Any other overlap of init with flow, and any overlap of init with
+ * the frames, is refused. Always enqueued eagerly (never a replayed graph, and
+ * the graph cache is not touched): the cache is keyed by the call's buffers
+ * and a captured graph holds its arguments, while a video loop changes the
+ * init buffer every call; one more key would evict the plain call's graphs.
+ * DIS_MEM_HOST is synchronous and stages through device buffers for max_batch
+ * pairs that the context allocates on the first such call
+ * (DIS_ERR_OUT_OF_MEMORY if that fails); the chunked host pipeline is not
+ * used. The context's init planes (a few KB) are allocated by dis_create.
+ * dis_flow_to_init is the reduction alone, into the caller's planes (device
+ * pointers 8-byte aligned; it touches no context workspace). */
+typedef enum dis_init_kind { DIS_INIT_COARSE = 0, DIS_INIT_FULLRES = 1 } dis_init_kind;
+dis_status dis_init_plane_size(dis_ctx* ctx, int* iw, int* ih);
+dis_status dis_flow_to_init(dis_ctx* ctx, int n, const float* flow, float* init_planes,
+                            dis_mem where, void* stream);
+dis_status dis_calc_batch_init_u8(dis_ctx* ctx, int n, const uint8_t* I0, const uint8_t* I1,
+                                  size_t stride, size_t pair_stride,
+                                  const float* init, int init_kind,
+                                  float* flow, dis_mem where, void* stream);
+
 /* Host-frame path (ABI v8): with DIS_MEM_HOST a batch runs in chunks of
  * chunk_pairs pairs (0 = auto, the default: about 64 MB of flow per chunk)
  * through two device slots; chunk j+1's upload, chunk j's computation and
@@ -264,7 +312,8 @@ dis_status dis_debug_dump(dis_ctx* ctx, int stage, int level, int pair, float* d
  * kernel: 0 = fused pyramid, 1 = patch search (all levels), 2 = patch search
  * (finest level only), 3 = fused densify+upsample+crop, 4 / 5 = variational
  * refinement's linearisation / SOR launches at the finest level (ABI v7;
- * timing replaces the refinement's per-level graphs by eager launches).
+ * timing replaces the refinement's per-level graphs by eager launches),
+ * 6 = the init-plane launch of a warm-started call (the reduction or the copy).
  * Enabling timing while
  * it is off starts a fresh measurement (accumulated launches and times are
  * cleared); dis_kernel_time returns the totals since then (the event pool

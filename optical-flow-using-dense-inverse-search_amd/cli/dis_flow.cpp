@@ -15,7 +15,10 @@
 // colour coding OF_<folder>/frame_NNNN_bw.png -- and frame_NNNN_bw.flo with
 // --flo -- and the forward flow's forward-backward consistency mask as the
 // 8-bit grey frame_NNNN_mask.png, 255 = consistent), --fb-alpha A1 A2 (the
-// check's constants, default 0.01 0.5).
+// check's constants, default 0.01 0.5), --warm-start (temporal warm start: each
+// pair's search starts from the previous pair's flow, the first pair from zero;
+// one pair per GPU call, so it is refused together with --batch N > 1 and with
+// --bidir -- the pairs of one batch run concurrently and have no previous flow).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -52,7 +55,7 @@ void usage()
                  "3. Add full settings\n"
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
-                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2"
+                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start"
               << std::endl;
 }
 
@@ -74,7 +77,7 @@ int main(int argc, char** argv)
     int draw_grid = 0;
     bool write_flo = false;
     int batch = 8, device = 0;
-    bool bidir = false;
+    bool bidir = false, warm_start = false, batch_given = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
 
     std::vector<std::string> pos;
@@ -84,10 +87,13 @@ int main(int argc, char** argv)
             write_flo = true;
         } else if (a == "--batch" && i + 1 < argc) {
             batch = std::atoi(argv[++i]);
+            batch_given = true;
         } else if (a == "--device" && i + 1 < argc) {
             device = std::atoi(argv[++i]);
         } else if (a == "--bidir") {
             bidir = true;
+        } else if (a == "--warm-start") {
+            warm_start = true;
         } else if (a == "--fb-alpha" && i + 2 < argc) {
             fb_alpha1 = (float)std::atof(argv[++i]);
             fb_alpha2 = (float)std::atof(argv[++i]);
@@ -121,6 +127,13 @@ int main(int argc, char** argv)
         return 2;
     }
     if (batch < 1) batch = 1;
+    if (warm_start && ((batch_given && batch > 1) || bidir)) {
+        std::cerr << "--warm-start seeds each pair from the previous pair's flow: it cannot be combined with "
+                  << (bidir ? "--bidir" : "--batch N > 1")
+                  << " (the pairs of one batch run concurrently, so there is no previous flow)" << std::endl;
+        return 2;
+    }
+    if (warm_start) batch = 1;
     struct stat sb;
     if (argc == 1 && ::stat(folder.c_str(), &sb) != 0) {  // no arguments and no default sequence here
         usage();
@@ -132,6 +145,7 @@ int main(int argc, char** argv)
     try {
         std::unique_ptr<dis::DenseInverseSearch> eng;
         int W = 0, H = 0;
+        std::vector<float> prev_flow;  // --warm-start: the previous pair's flow (empty: start cold)
         for (int i0 = start; i0 < end; i0 += batch) {
             const int n = std::min(batch, end - i0);
             std::vector<png::Gray> frames;
@@ -143,6 +157,7 @@ int main(int argc, char** argv)
                 W = frames[0].width;
                 H = frames[0].height;
                 eng.reset(new dis::DenseInverseSearch(p, W, H, batch, device));
+                prev_flow.clear();
             }
             std::vector<uint8_t> I0((size_t)n * W * H), I1((size_t)n * W * H);
             for (int k = 0; k < n; ++k) {
@@ -162,6 +177,10 @@ int main(int argc, char** argv)
                 dis::flowConsistency(flow.data(), flow_bw.data(), n, W, H, mask.data(), nullptr, fb_alpha1, fb_alpha2,
                                      DIS_MEM_HOST, nullptr, device);
                 dis::check(dis_flow_color(flow_bw.data(), n, W, H, -1.0f, bgr_bw.data(), DIS_MEM_HOST, nullptr, device));
+            } else if (warm_start) {
+                eng->calc(I0.data(), I1.data(), flow.data(), prev_flow.empty() ? nullptr : prev_flow.data(),
+                          dis::InitKind::FULLRES);
+                prev_flow = flow;
             } else {
                 eng->calc_batch(n, I0.data(), I1.data(), flow.data());
             }

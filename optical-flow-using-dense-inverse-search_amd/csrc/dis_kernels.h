@@ -33,6 +33,8 @@ struct SearchArgs {
     long long plane_stride;    // floats per pair
     long long plane_off;       // this level's offset in the plane stack
     long long dense_stride;    // float2 per pair (dense stack), dense_coarse pre-offset
+    int coarse_ld;             // row stride of dense_coarse in float2: W / 2 (level l+1's width), or the
+                               //   init plane's iw at a warm-started coarsest level (W_C may be odd)
     long long u_stride;        // float2 per pair (patch stack), u_out pre-offset
     int phys_pad;              // 0: virtual padding (clamp image / zero gradients);
                                // >0: planes are physically padded by this many pixels
@@ -61,6 +63,8 @@ struct Search8Args {
     int lanes_per_patch;      // 1, 2, 4 or 8 (k_search8<LPP>)
     const float2* dense_coarse;  // non-null: init from the coarser level's DENSE flow (variational
     long long dense_stride;      //   refinement on) instead of u_coarse; float2 per pair
+    int coarse_ld;               // row stride of dense_coarse in float2: W / 2, or the init plane's iw at a
+                                 //   warm-started coarsest level (wave-uniform, read once per patch)
     int tile_cap;             // > 0: usable tile rows / columns capped at this (variant 9, a parity-test
                               //   switch that sends most blocks through the fallback list); 0 = the full tile
     int* fb_count;            // LPP 1/2: blocks too spread for the LDS tile are listed here
@@ -172,6 +176,16 @@ size_t flow_color_ws_words(int n);
 long long flow_consistency_blocks(int n, int W, int H);  // grid size of the launch
 hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int W, int H, float alpha1,
                                    float alpha2, uint8_t* mask, float* err, hipStream_t s, Timing t = {});
+
+// The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
+// ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
+// W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in
+// one launch; launch_init_copy is the sanitising copy of `count` floats of
+// caller-made planes.
+void init_plane_size(const Geometry& g, int* iw, int* ih);
+hipError_t launch_flow_to_init(const float* flow, float* planes, int n, const Geometry& g, hipStream_t s,
+                               Timing t = {});
+hipError_t launch_init_copy(const float* src, float* dst, long long count, hipStream_t s, Timing t = {});
 
 // Variational refinement of one level's dense flow (dis_varref.hip).
 constexpr int kVarRefPlanes = 8;   // per-pair workspace planes

@@ -158,11 +158,11 @@ __global__ void __launch_bounds__(256) k_sobel(const float* __restrict__ img, fl
 // Coarse-to-fine initialisation (src/patch_grid.cpp:108-119): nearest (floor)
 // lookup of the coarser dense flow at (floor(ref/2)), times 2.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void init_from_coarser(const float2* __restrict__ dense_c, int Wl,
+__device__ __forceinline__ void init_from_coarser(const float2* __restrict__ dense_c, int ld,
                                                   float refx, float refy, float* ix, float* iy)
 {
     const int x = (int)floorf(refx / 2), y = (int)floorf(refy / 2);
-    const float2 f = dense_c[(size_t)y * (Wl / 2) + x];
+    const float2 f = dense_c[(size_t)y * ld + x];
     *ix = f.x * 2;
     *iy = f.y * 2;
 }
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(64) k_search_generic(SearchArgs a)
 
     float inx = 0.0f, iny = 0.0f;
     if (a.dense_coarse)
-        init_from_coarser(a.dense_coarse + (size_t)pair * a.dense_stride, W, refx, refy, &inx, &iny);
+        init_from_coarser(a.dense_coarse + (size_t)pair * a.dense_stride, a.coarse_ld, refx, refy, &inx, &iny);
 
     float u0 = inx, u1 = iny;
     const float sx = refx + u0, sy = refy + u1;  // start position (src/patch.cpp:125-128)

@@ -20,6 +20,7 @@
 
 #include <dlfcn.h>
 
+#include "dis_alias.h"
 #include "dis_kernels.h"
 #include "dis_plan.h"
 
@@ -309,6 +310,16 @@ struct dis_ctx {
     // pairs (both frames; both flows), made on the first such call
     uint8_t* bd_in = nullptr;
     float2* bd_out = nullptr;
+    // warm start (dis_calc_batch_init_u8): the context's init planes, iw x ih
+    // float2 per pair for max_batch pairs; `warm` is set for the duration of a
+    // warm-started call's enqueue (the coarsest level then starts from them)
+    float2* init = nullptr;
+    int iw = 0, ih = 0;
+    bool warm = false;
+    // ... and, for host pointers, device staging for max_batch pairs (frames;
+    // init input and flow), made on the first such call
+    uint8_t* wi_in = nullptr;
+    float2* wi_out = nullptr;
     // kernel timing
     int timing = 0;
     struct Rec {
@@ -318,7 +329,7 @@ struct dis_ctx {
     std::vector<hipEvent_t> pool;
     std::vector<Rec> recs;
     size_t pool_next = 0;
-    static constexpr int kKinds = 6;  // dis_kernel_time classes
+    static constexpr int kKinds = 7;  // dis_kernel_time classes
     int launches[kKinds] = {};
     double total_ms[kKinds] = {};
     long long dropped = 0;  // records lost to a failed event creation (dis_kernel_time fails then)
@@ -368,6 +379,12 @@ void free_ws(dis_ctx* c)
     hipFree(c->bd_out);
     c->bd_in = nullptr;
     c->bd_out = nullptr;
+    hipFree(c->init);
+    hipFree(c->wi_in);
+    hipFree(c->wi_out);
+    c->init = nullptr;
+    c->wi_in = nullptr;
+    c->wi_out = nullptr;
     c->img0 = c->img1 = c->dx = c->dy = nullptr;
     c->pu = c->dense = nullptr;
 }
@@ -645,8 +662,18 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
         a.plane_stride = g.plane_stride;
         a.plane_off = L.plane_off;
         a.dense_stride = g.dense_stride;
+        a.coarse_ld = L.W / 2;
         a.u_stride = g.u_stride;
         a.phys_pad = 0;
+        // warm start: the coarsest level starts from the context's init plane as
+        // every finer level does from the dense flow above it
+        const bool warm_level = c->warm && l == g.C;
+        const long long init_stride = (long long)c->iw * c->ih;
+        if (warm_level) {
+            a.dense_coarse = c->init + (size_t)p0 * init_stride;
+            a.dense_stride = init_stride;
+            a.coarse_ld = c->iw;
+        }
         a.W = L.W;
         a.H = L.H;
         a.steps = L.steps;
@@ -669,9 +696,15 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
                 b.c_W = g.lv[l + 1].W;
                 b.c_H = g.lv[l + 1].H;
             }
+            b.coarse_ld = L.W / 2;
             if (vr && l < g.C) {  // refined dense flows: init from the coarser level's dense field
                 b.dense_coarse = dense + g.lv[l + 1].dense_off;
                 b.dense_stride = g.dense_stride;
+            }
+            if (warm_level) {  // (paper mode too: no coarser patches, the plain dense-init branch)
+                b.dense_coarse = a.dense_coarse;
+                b.dense_stride = init_stride;
+                b.coarse_ld = c->iw;
             }
             if (b.lanes_per_patch == 64 && (paper || b.fma)) {  // exact, non-paper only
                 b.lanes_per_patch = 2;
@@ -1388,6 +1421,10 @@ dis_status dis_create(dis_ctx** out, const dis_params* params, int width, int he
         ok = hipMalloc(&c->fb, sizeof(int) * off) == hipSuccess &&
              hipMemset(c->fb, 0, sizeof(int) * dis_ctx::kMaxSub * kFbCounters) == hipSuccess;
     }
+    if (ok) {  // warm start: the init planes (a few KB)
+        dis::init_plane_size(g, &c->iw, &c->ih);
+        ok = hipMalloc(&c->init, sizeof(float2) * (size_t)c->iw * c->ih * B) == hipSuccess;
+    }
     if (ok && params->var_refine_iters > 0) {
         c->vr_plane = (long long)g.lv[g.F].W * g.lv[g.F].H;  // the largest refined level
         ok = hipMalloc(&c->vr_ws, sizeof(float) * dis::kVarRefPlanes * c->vr_plane * B) == hipSuccess;
@@ -1523,6 +1560,136 @@ dis_status dis_calc_bidir_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const u
     }
     DIS_HIP(hipMemcpyAsync(flow_fw, dfw, fbytes, hipMemcpyDeviceToHost, s));
     DIS_HIP(hipMemcpyAsync(flow_bw, dbw, fbytes, hipMemcpyDeviceToHost, s));
+    DIS_HIP(hipStreamSynchronize(s));
+    return DIS_OK;
+}
+
+dis_status dis_init_plane_size(dis_ctx* c, int* iw, int* ih)
+{
+    if (!c || !iw || !ih) return fail(DIS_ERR_INVALID_ARGUMENT, "null argument");
+    *iw = c->iw;
+    *ih = c->ih;
+    return DIS_OK;
+}
+
+// The reduction alone, into the caller's planes (no context workspace is
+// touched: nothing to order against the context's other calls).
+dis_status dis_flow_to_init(dis_ctx* c, int n, const float* flow, float* init_planes, dis_mem where, void* stream)
+{
+    if (!flow || !init_planes) return fail(DIS_ERR_INVALID_ARGUMENT, "null flow or init_planes pointer");
+    if (n < 1 || n > 65535) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, 65535]");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    DIS_HIP(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (where == DIS_MEM_DEVICE) {
+        if (reinterpret_cast<uintptr_t>(flow) & 7 || reinterpret_cast<uintptr_t>(init_planes) & 7)
+            return fail(DIS_ERR_INVALID_ARGUMENT, "flow and init_planes must be 8-byte aligned");
+        DIS_HIP(dis::launch_flow_to_init(flow, init_planes, n, c->g, s));
+        return DIS_OK;
+    }
+    const size_t fbytes = sizeof(float2) * (size_t)c->g.W * c->g.H * n;
+    const size_t pbytes = sizeof(float2) * (size_t)c->iw * c->ih * n;
+    float *dflow = nullptr, *dplanes = nullptr;
+    dis_status rc = DIS_OK;
+    if (hipMalloc(&dflow, fbytes) != hipSuccess || hipMalloc(&dplanes, pbytes) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
+    } else if (hipMemcpyAsync(dflow, flow, fbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+               dis::launch_flow_to_init(dflow, dplanes, n, c->g, s) != hipSuccess ||
+               hipMemcpyAsync(init_planes, dplanes, pbytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               hipStreamSynchronize(s) != hipSuccess) {
+        rc = fail(DIS_ERR_DEVICE, "flow to init plane reduction failed");
+    }
+    hipFree(dflow);
+    hipFree(dplanes);
+    return rc;
+}
+
+// Warm start: fill the context's init planes from `init` (the reduction or the
+// sanitising copy), then the plain level chain with the coarsest level reading
+// them. Always the eager enqueue: the main graph cache's key and captured
+// arguments know nothing of an init buffer, and a video loop hands over a
+// different (or the just-written) buffer every call.
+dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, size_t stride,
+                                  size_t pair_stride, const float* init, int init_kind, float* flow, dis_mem where,
+                                  void* stream)
+{
+    if (!init) return dis_calc_batch_u8(c, n, I0, I1, stride, pair_stride, flow, where, stream);
+    // (what needs no context first: checked the same with or without a device)
+    if (!I0 || !I1 || !flow) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
+    if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    if (init_kind != DIS_INIT_COARSE && init_kind != DIS_INIT_FULLRES)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "init_kind must be DIS_INIT_COARSE or DIS_INIT_FULLRES");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (n > c->max_batch) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    const int W = c->g.W, H = c->g.H;
+    if (stride == 0) stride = (size_t)W;
+    if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
+    if (pair_stride == 0) pair_stride = stride * H;
+    if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
+    const size_t fpp = (size_t)W * H;                 // float2 per flow
+    const size_t ipp = (size_t)c->iw * c->ih;         // float2 per init plane
+    const size_t fbytes = sizeof(float2) * fpp * (size_t)n;
+    const size_t ibytes = init_kind == DIS_INIT_FULLRES ? fbytes : sizeof(float2) * ipp * (size_t)n;
+    const size_t frame_bytes = (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W;
+    if (const char* why = dis::check_init_aliasing(reinterpret_cast<uintptr_t>(init), ibytes,
+                                                   reinterpret_cast<uintptr_t>(flow), fbytes,
+                                                   reinterpret_cast<uintptr_t>(I0), reinterpret_cast<uintptr_t>(I1),
+                                                   frame_bytes))
+        return fail(DIS_ERR_INVALID_ARGUMENT, why);
+    if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(init) & 7))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "init must be 8-byte aligned");
+    DIS_HIP(hipSetDevice(c->device));
+    // Fill the planes on `s`, then run the chain on `s`: every sub-batch stream
+    // forks from `s` after the fill, so the planes are complete -- and `init`
+    // has been read to the end -- before any kernel of the chain starts, the
+    // one that writes `flow` included. That is what lets init be flow.
+    auto enqueue = [&](const uint8_t* f0, const uint8_t* f1, size_t st, size_t pst, const float* in, float2* out,
+                       hipStream_t s) -> dis_status {
+        if (c->needs_wait(s)) DIS_HIP(hipStreamWaitEvent(s, c->done, 0));  // the planes are workspace
+        if (init_kind == DIS_INIT_FULLRES)
+            DIS_HIP(dis::launch_flow_to_init(in, reinterpret_cast<float*>(c->init), n, c->g, s, timing(c, 6)));
+        else
+            DIS_HIP(dis::launch_init_copy(in, reinterpret_cast<float*>(c->init), (long long)(2 * ipp) * n, s,
+                                          timing(c, 6)));
+        std::lock_guard<std::mutex> lock(pool_mutex(c->device));  // eager enqueue onto the pooled streams
+        c->warm = true;
+        const dis_status r = run_batches(c, n, f0, f1, st, pst, out, s);
+        c->warm = false;
+        return r;
+    };
+    if (where == DIS_MEM_DEVICE)
+        return enqueue(I0, I1, stride, pair_stride, init, reinterpret_cast<float2*>(flow),
+                       reinterpret_cast<hipStream_t>(stream));
+    // host memory: synchronous, staged through device buffers for max_batch
+    // pairs made on the first such call (the chunked pipeline of
+    // dis_calc_batch_u8 is not used here)
+    const size_t B = (size_t)c->max_batch;
+    if (!c->wi_in || !c->wi_out) {
+        if ((!c->wi_in && hipMalloc(&c->wi_in, 2 * fpp * B) != hipSuccess) ||
+            (!c->wi_out && hipMalloc(&c->wi_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(DIS_ERR_OUT_OF_MEMORY, "warm-start host-path device buffer allocation failed");
+        }
+    }
+    const hipStream_t s = c->own;
+    uint8_t* const d0 = c->wi_in;
+    uint8_t* const d1 = c->wi_in + fpp * B;
+    float2* const dflow = c->wi_out;
+    float2* const dinit = c->wi_out + fpp * B;  // (ipp <= fpp: a plane is never larger than a flow)
+    for (int k = 0; k < n; ++k) {
+        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
+        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
+    }
+    DIS_HIP(hipMemcpyAsync(dinit, init, ibytes, hipMemcpyHostToDevice, s));
+    const dis_status st = enqueue(d0, d1, (size_t)W, fpp, reinterpret_cast<const float*>(dinit), dflow, s);
+    if (st != DIS_OK) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+    DIS_HIP(hipMemcpyAsync(flow, dflow, fbytes, hipMemcpyDeviceToHost, s));
     DIS_HIP(hipStreamSynchronize(s));
     return DIS_OK;
 }
@@ -1833,6 +2000,7 @@ dis_status dis_flow_from_pyramids(const float* const* img_first, const float* co
         a.plane_stride = tot;
         a.plane_off = poff[l];
         a.dense_stride = g.dense_stride;
+        a.coarse_ld = L.W / 2;
         a.u_stride = g.u_stride;
         a.phys_pad = img_padding;
         a.W = L.W;

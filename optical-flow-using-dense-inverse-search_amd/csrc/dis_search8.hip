@@ -782,7 +782,7 @@ __device__ __forceinline__ void search_block(const Search8Args& a, int bxi, int 
     if (kPaper && uc) {
     } else if (a.dense_coarse && active) {
         // from the coarser level's dense flow (refined): src/patch_grid.cpp:108-119
-        const float2 d = a.dense_coarse[(size_t)pair * a.dense_stride + (size_t)(iry >> 1) * (W / 2) + (irx >> 1)];
+        const float2 d = a.dense_coarse[(size_t)pair * a.dense_stride + (size_t)(iry >> 1) * a.coarse_ld + (irx >> 1)];
         ix = d.x * 2;
         iy = d.y * 2;
     } else if (uc && active) {

@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_search_wave(Search8Args a)
     // initialisation from the coarser level (src/patch_grid.cpp:108-119)
     float ix = 0.0f, iy = 0.0f;
     if (a.dense_coarse) {
-        const float2 d = a.dense_coarse[(size_t)pair * a.dense_stride + (size_t)(iry >> 1) * (W / 2) + (irx >> 1)];
+        const float2 d = a.dense_coarse[(size_t)pair * a.dense_stride + (size_t)(iry >> 1) * a.coarse_ld + (irx >> 1)];
         ix = d.x * 2;
         iy = d.y * 2;
     } else if (a.u_coarse) {

@@ -49,6 +49,10 @@ STAGE_IMG0, STAGE_IMG1, STAGE_DX0, STAGE_DY0, STAGE_PATCH_U, STAGE_DENSE, STAGE_
 PRECISION_EXACT, PRECISION_FMA = 0, 1
 
 KERNEL_PYRAMID, KERNEL_SEARCH, KERNEL_SEARCH_FINEST, KERNEL_DENSIFY, KERNEL_VR_LIN, KERNEL_VR_SOR = range(6)
+KERNEL_INIT = 6  # the init-plane launch of a warm-started call
+
+INIT_COARSE, INIT_FULLRES = 0, 1
+_INIT_KINDS = {"coarse": INIT_COARSE, "fullres": INIT_FULLRES, INIT_COARSE: INIT_COARSE, INIT_FULLRES: INIT_FULLRES}
 
 # Every symbol include/dis_abi.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -60,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "dis_read_flo", "dis_write_flo", "dis_build_kind", "dis_set_host_pipeline", "dis_host_pipeline_info",
     "dis_host_alloc", "dis_host_free", "dis_batch_stream_plan", "dis_check_stream_plan",
     "dis_calc_bidir_batch_u8", "dis_flow_consistency",
+    "dis_init_plane_size", "dis_flow_to_init", "dis_calc_batch_init_u8",
 )
 
 
@@ -172,6 +177,10 @@ def lib() -> ctypes.CDLL:
             L.dis_calc_bidir_batch_u8.argtypes = [V, I, V, V, Z, Z, V, V, I, V]
         if hasattr(L, "dis_flow_consistency"):
             L.dis_flow_consistency.argtypes = [V, V, I, I, I, F, F, V, V, I, V, I]
+        if hasattr(L, "dis_calc_batch_init_u8"):  # (added within v8)
+            L.dis_init_plane_size.argtypes = [V, P(I), P(I)]
+            L.dis_flow_to_init.argtypes = [V, I, V, V, I, V]
+            L.dis_calc_batch_init_u8.argtypes = [V, I, V, V, Z, Z, V, I, V, I, V]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -334,26 +343,97 @@ class DenseInverseSearch:
         except Exception:
             pass
 
-    def calc(self, I0: np.ndarray, I1: np.ndarray) -> np.ndarray:
-        """u8 H x W frames (host) -> H x W x 2 float32 flow (host)."""
-        return self.calc_batch(I0[None], I1[None])[0]
+    def init_plane_size(self):
+        """(iw, ih) of one pair's init plane (dis_init_plane_size): half the
+        padded frame's coarsest level, rounded up."""
+        iw, ih = ctypes.c_int(), ctypes.c_int()
+        _check(lib().dis_init_plane_size(self._ctx, ctypes.byref(iw), ctypes.byref(ih)))
+        return iw.value, ih.value
 
-    def calc_batch(self, I0: np.ndarray, I1: np.ndarray) -> np.ndarray:
+    def _plane_shape(self):
+        # the same size without a library call (shape checks raise before any)
+        sf = 1 << self.params.coarsest_scale
+        wc = (self.width + sf - 1) // sf
+        hc = (self.height + sf - 1) // sf
+        return (hc + 1) // 2, (wc + 1) // 2
+
+    def _check_init(self, init, init_kind, n: int):
+        """Validate an init array for n pairs -> (contiguous float32 array, kind)."""
+        if init_kind not in _INIT_KINDS or isinstance(init_kind, bool):
+            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"init_kind must be 'fullres' or 'coarse', not {init_kind!r}")
+        kind = _INIT_KINDS[init_kind]
+        a = np.ascontiguousarray(init, dtype=np.float32)
+        hw = (self.height, self.width) if kind == INIT_FULLRES else self._plane_shape()
+        if a.shape != (n,) + hw + (2,):
+            raise DisError(DIS_ERR_INVALID_ARGUMENT,
+                           f"init must be {(n,) + hw + (2,)} for init_kind {init_kind!r}, not {a.shape}")
+        return a, kind
+
+    def flow_to_init(self, flows: np.ndarray) -> np.ndarray:
+        """Full-resolution (H, W, 2) or (n, H, W, 2) flows -> their init planes
+        (ih, iw, 2) / (n, ih, iw, 2) (dis_flow_to_init: the reduction alone)."""
+        f = np.ascontiguousarray(flows, dtype=np.float32)
+        single = f.ndim == 3
+        if single:
+            f = f[None]
+        if f.ndim != 4 or f.shape[1:] != (self.height, self.width, 2):
+            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"flows must be (n, {self.height}, {self.width}, 2)")
+        out = np.empty((f.shape[0],) + self._plane_shape() + (2,), np.float32)
+        _check(lib().dis_flow_to_init(self._ctx, f.shape[0], _ptr(f), _ptr(out), MEM_HOST, None))
+        return out[0] if single else out
+
+    def calc(self, I0: np.ndarray, I1: np.ndarray, init=None, init_kind="fullres") -> np.ndarray:
+        """u8 H x W frames (host) -> H x W x 2 float32 flow (host). init: the
+        search's start, a full-resolution (H, W, 2) flow (init_kind "fullres",
+        e.g. the previous pair's result) or an init plane (ih, iw, 2) ("coarse")."""
+        return self.calc_batch(I0[None], I1[None], None if init is None else np.asarray(init)[None], init_kind)[0]
+
+    def calc_batch(self, I0: np.ndarray, I1: np.ndarray, init=None, init_kind="fullres") -> np.ndarray:
         I0 = np.ascontiguousarray(I0, dtype=np.uint8)
         I1 = np.ascontiguousarray(I1, dtype=np.uint8)
         if I0.shape != I1.shape or I0.ndim != 3 or I0.shape[1:] != (self.height, self.width):
             raise DisError(DIS_ERR_INVALID_ARGUMENT, f"frames must be (n, {self.height}, {self.width})")
         n = I0.shape[0]
+        if init is not None:
+            init, kind = self._check_init(init, init_kind, n)
         flow = np.empty((n, self.height, self.width, 2), np.float32)
-        _check(lib().dis_calc_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
-                                       self.width * self.height, _ptr(flow), MEM_HOST, None))
+        if init is None:
+            _check(lib().dis_calc_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
+                                           self.width * self.height, _ptr(flow), MEM_HOST, None))
+        else:
+            _check(lib().dis_calc_batch_init_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
+                                                self.width * self.height, _ptr(init), kind, _ptr(flow),
+                                                MEM_HOST, None))
         return flow
 
     def calc_device(self, n: int, I0_ptr: int, I1_ptr: int, flow_ptr: int, stream: int = 0,
-                    stride: int = 0, pair_stride: int = 0) -> None:
-        """Asynchronous calc on device-resident buffers (raw device pointers)."""
-        _check(lib().dis_calc_batch_u8(self._ctx, n, I0_ptr, I1_ptr, stride, pair_stride, flow_ptr,
-                                       MEM_DEVICE, stream or None))
+                    stride: int = 0, pair_stride: int = 0, init_ptr: int = 0, init_kind="fullres") -> None:
+        """Asynchronous calc on device-resident buffers (raw device pointers).
+        init_ptr: n full-resolution flows ("fullres"; may be flow_ptr itself) or
+        n init planes ("coarse") to start the search from."""
+        if not init_ptr:
+            _check(lib().dis_calc_batch_u8(self._ctx, n, I0_ptr, I1_ptr, stride, pair_stride, flow_ptr,
+                                           MEM_DEVICE, stream or None))
+            return
+        if init_kind not in _INIT_KINDS or isinstance(init_kind, bool):
+            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"init_kind must be 'fullres' or 'coarse', not {init_kind!r}")
+        _check(lib().dis_calc_batch_init_u8(self._ctx, n, I0_ptr, I1_ptr, stride, pair_stride, init_ptr,
+                                            _INIT_KINDS[init_kind], flow_ptr, MEM_DEVICE, stream or None))
+
+    def flow_to_init_device(self, n: int, flow_ptr: int, planes_ptr: int, stream: int = 0) -> None:
+        """dis_flow_to_init on raw device pointers, asynchronous on `stream`."""
+        _check(lib().dis_flow_to_init(self._ctx, n, flow_ptr, planes_ptr, MEM_DEVICE, stream or None))
+
+    def track(self, frames):
+        """Generator over an iterable of u8 H x W frames: yields the flow of
+        each consecutive pair, warm-started from the flow of the pair before
+        (the first pair is cold)."""
+        prev_frame, prev_flow = None, None
+        for f in frames:
+            if prev_frame is not None:
+                prev_flow = self.calc(prev_frame, f, init=prev_flow)
+                yield prev_flow
+            prev_frame = f
 
     def calc_bidir(self, I0: np.ndarray, I1: np.ndarray):
         """u8 H x W frames (host) -> (flow I0->I1, flow I1->I0), one pyramid."""
