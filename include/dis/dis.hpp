@@ -5,6 +5,9 @@
 //                             (the per-pair body of src/main.cpp:135-198);
 //                             calc(I0, I1, flow_fw, flow_bw) for both directions
 //   dis::flowConsistency      forward-backward consistency mask of two fields
+//   dis::FlowFormat, dis::half_bits, dis::flowConvert
+//                             f16 flow output (set_flow_format) and the
+//                             conversion between the two formats
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -37,6 +40,11 @@ enum class Preset {
 
 // the two forms of a warm start's `init` argument (dis_init_kind)
 enum class InitKind { COARSE = DIS_INIT_COARSE, FULLRES = DIS_INIT_FULLRES };
+
+// the format of every full-resolution flow an engine writes and reads
+// (dis_flow_format); an F16 flow is an array of IEEE binary16 bit patterns
+enum class FlowFormat { F32 = DIS_FLOW_F32, F16 = DIS_FLOW_F16 };
+using half_bits = uint16_t;
 
 class Error : public std::runtime_error {
 public:
@@ -79,13 +87,25 @@ public:
     DenseInverseSearch(const DenseInverseSearch&) = delete;
     DenseInverseSearch& operator=(const DenseInverseSearch&) = delete;
     DenseInverseSearch(DenseInverseSearch&& o) noexcept
-        : ctx_(std::exchange(o.ctx_, nullptr)), params_(o.params_), width_(o.width_), height_(o.height_)
+        : ctx_(std::exchange(o.ctx_, nullptr)), params_(o.params_), width_(o.width_), height_(o.height_),
+          format_(o.format_)
     {
     }
+
+    // Flow format (dis_set_flow_format), F32 by default. The float* flow
+    // overloads below throw while it is F16, the half_bits* ones unless it is:
+    // a buffer of the wrong element size is never handed to the engine.
+    void set_flow_format(FlowFormat f)
+    {
+        check(dis_set_flow_format(ctx_, static_cast<int>(f)));
+        format_ = f;
+    }
+    FlowFormat flow_format() const { return format_; }
 
     // Host u8 frames (row stride in bytes, 0 = width) -> host W*H*2 flow (u,v).
     void calc(const uint8_t* I0, const uint8_t* I1, float* flow, size_t stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_u8(ctx_, I0, I1, stride, flow, DIS_MEM_HOST, nullptr));
     }
     std::vector<float> calc(const std::vector<uint8_t>& I0, const std::vector<uint8_t>& I1)
@@ -96,37 +116,70 @@ public:
         calc(I0.data(), I1.data(), flow.data());
         return flow;
     }
+    // ... -> host W*H*2 f16 flow (an F16 engine)
+    void calc(const uint8_t* I0, const uint8_t* I1, half_bits* flow, size_t stride = 0)
+    {
+        need(FlowFormat::F16);
+        check(dis_calc_u8(ctx_, I0, I1, stride, as_flow(flow), DIS_MEM_HOST, nullptr));
+    }
     // Device-resident frames/flow; asynchronous on `stream` (hipStream_t).
     void calc_device(const uint8_t* dI0, const uint8_t* dI1, float* dflow, void* stream = nullptr, size_t stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_u8(ctx_, dI0, dI1, stride, dflow, DIS_MEM_DEVICE, stream));
+    }
+    // (an F16 engine: dflow 4-byte aligned)
+    void calc_device(const uint8_t* dI0, const uint8_t* dI1, half_bits* dflow, void* stream = nullptr,
+                     size_t stride = 0)
+    {
+        need(FlowFormat::F16);
+        check(dis_calc_u8(ctx_, dI0, dI1, stride, as_flow(dflow), DIS_MEM_DEVICE, stream));
     }
     // n pairs: frames at I0 + k*pair_stride, flows at flow + k*W*H*2.
     void calc_batch(int n, const uint8_t* I0, const uint8_t* I1, float* flow, dis_mem where = DIS_MEM_HOST,
                     void* stream = nullptr, size_t stride = 0, size_t pair_stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_batch_u8(ctx_, n, I0, I1, stride, pair_stride, flow, where, stream));
+    }
+    void calc_batch(int n, const uint8_t* I0, const uint8_t* I1, half_bits* flow, dis_mem where = DIS_MEM_HOST,
+                    void* stream = nullptr, size_t stride = 0, size_t pair_stride = 0)
+    {
+        need(FlowFormat::F16);
+        check(dis_calc_batch_u8(ctx_, n, I0, I1, stride, pair_stride, as_flow(flow), where, stream));
     }
     // Both directions in one call (dis_calc_bidir_batch_u8): flow_fw is what
     // calc(I0, I1, .) gives, flow_bw what calc(I1, I0, .) gives, bit for bit;
     // each frame's pyramid is built once.
     void calc(const uint8_t* I0, const uint8_t* I1, float* flow_fw, float* flow_bw, size_t stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_bidir_batch_u8(ctx_, 1, I0, I1, stride, 0, flow_fw, flow_bw, DIS_MEM_HOST, nullptr));
     }
     void calc_bidir_batch(int n, const uint8_t* I0, const uint8_t* I1, float* flow_fw, float* flow_bw,
                           dis_mem where = DIS_MEM_HOST, void* stream = nullptr, size_t stride = 0,
                           size_t pair_stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_bidir_batch_u8(ctx_, n, I0, I1, stride, pair_stride, flow_fw, flow_bw, where, stream));
+    }
+    void calc_bidir_batch(int n, const uint8_t* I0, const uint8_t* I1, half_bits* flow_fw, half_bits* flow_bw,
+                          dis_mem where = DIS_MEM_HOST, void* stream = nullptr, size_t stride = 0,
+                          size_t pair_stride = 0)
+    {
+        need(FlowFormat::F16);
+        check(dis_calc_bidir_batch_u8(ctx_, n, I0, I1, stride, pair_stride, as_flow(flow_fw), as_flow(flow_bw), where,
+                                      stream));
     }
     // Warm start (dis_calc_batch_init_u8): the coarsest level starts from
     // `init` -- a full-resolution W*H*2 flow such as the previous pair's result
     // (InitKind::FULLRES; it may be `flow` itself) or an init plane of
     // initPlaneSize() vectors (InitKind::COARSE). init == nullptr is the plain
-    // calc.
+    // calc. (float flows: an F32 engine; an F16 engine's warm start goes
+    // through the C-ABI with its format-typed pointers.)
     void calc(const uint8_t* I0, const uint8_t* I1, float* flow, const float* init, InitKind kind, size_t stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_batch_init_u8(ctx_, 1, I0, I1, stride, 0, init, static_cast<int>(kind), flow, DIS_MEM_HOST,
                                      nullptr));
     }
@@ -134,6 +187,7 @@ public:
                          dis_mem where = DIS_MEM_HOST, void* stream = nullptr, size_t stride = 0,
                          size_t pair_stride = 0)
     {
+        need(FlowFormat::F32);
         check(dis_calc_batch_init_u8(ctx_, n, I0, I1, stride, pair_stride, init, static_cast<int>(kind), flow, where,
                                      stream));
     }
@@ -148,6 +202,7 @@ public:
     void flow_to_init(int n, const float* flow, float* init_planes, dis_mem where = DIS_MEM_HOST,
                       void* stream = nullptr)
     {
+        need(FlowFormat::F32);
         check(dis_flow_to_init(ctx_, n, flow, init_planes, where, stream));
     }
     void set_concurrency(int streams) { check(dis_set_concurrency(ctx_, streams)); }
@@ -163,9 +218,20 @@ public:
     dis_ctx* handle() const { return ctx_; }
 
 private:
+    void need(FlowFormat f) const
+    {
+        if (format_ != f)
+            throw Error(DIS_ERR_INVALID_ARGUMENT, f == FlowFormat::F16
+                                                      ? "dis: half_bits flow on an engine whose flow format is F32"
+                                                      : "dis: float flow on an engine whose flow format is F16");
+    }
+    // the ABI's flow parameters are format-typed float*
+    static float* as_flow(half_bits* p) { return reinterpret_cast<float*>(p); }
+
     dis_ctx* ctx_ = nullptr;
     dis_params params_;
     int width_, height_;
+    FlowFormat format_ = FlowFormat::F32;
 };
 
 // Middlebury colour coding (src/color_coding.cpp draw_optical_flow) of n
@@ -185,6 +251,16 @@ inline void flowConsistency(const float* fw, const float* bw, int n, int width, 
                             dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
 {
     check(dis_flow_consistency(fw, bw, n, width, height, alpha1, alpha2, mask, err, where, stream, device));
+}
+
+// `count` flow values between the two formats (dis_flow_convert), on the GPU:
+// F32 -> F16 is the engine's own narrowing (round to nearest even), F16 -> F32
+// is exact. src / dst point at float or half_bits as their format says.
+inline void flowConvert(const void* src, FlowFormat src_format, void* dst, FlowFormat dst_format, size_t count,
+                        dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_convert(src, static_cast<int>(src_format), dst, static_cast<int>(dst_format), count, where, stream,
+                           device));
 }
 
 // Middlebury .flo files (src/IO_flow.cpp ReadFlowFile / SaveFlowFile).

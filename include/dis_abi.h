@@ -109,14 +109,58 @@ dis_status dis_create(dis_ctx** out, const dis_params* params, int width, int he
                       int max_batch, int device);
 dis_status dis_destroy(dis_ctx* ctx);
 
+/* Flow output format (added within ABI v8: purely additive, DIS_ABI_VERSION
+ * unchanged; the reference writes float flows only). Context state, like
+ * dis_set_precision; DIS_FLOW_F32 is the default, and with it every result is
+ * bit for bit what it was. With DIS_FLOW_F16 every full-resolution flow a
+ * dis_calc_* call of this context writes -- dis_calc_u8, dis_calc_batch_u8,
+ * both outputs of dis_calc_bidir_batch_u8, dis_calc_batch_init_u8 -- holds
+ * W*H*2 IEEE binary16 values instead of floats: (u,v) interleaved, pair stride
+ * W*H*2 halves. The `float*` flow parameters keep their C type and are
+ * format-typed: they point at floats or at halves as the context's format says.
+ * Each stored half is the float the F32 format would have stored, converted
+ * once: round to nearest, ties to even; subnormals kept; |v| >= 65520 gives
+ * +-inf; NaN stays NaN. The write-out kernels narrow in their stores: no f32
+ * intermediate, no extra launch. In DIS_PRECISION_EXACT the F16 output is the
+ * oracle's flow narrowed, bit for bit.
+ * A DIS_INIT_FULLRES init and dis_flow_to_init's flow are read in the
+ * context's format too (a previous call's output, the output buffer itself
+ * included, stays a valid argument): the halves are widened exactly, then
+ * sanitised and reduced as floats are. DIS_INIT_COARSE planes, the context's
+ * init planes, dis_flow_to_init's output, the debug dumps (DIS_STAGE_*) and
+ * dis_flow_from_pyramids stay f32. dis_flow_color and dis_flow_consistency
+ * take f32 fields only: dis_flow_convert is how f16 flows reach them.
+ * Alignment of DIS_MEM_DEVICE flow pointers in DIS_FLOW_F16: 4 bytes (one
+ * (u,v) pair), else DIS_ERR_INVALID_ARGUMENT; a pointer that is 8-byte aligned
+ * (and an even W) gets 8-byte stores of two pixels, any other one 4-byte store
+ * per pixel. The host pipeline's chunks and device slots, the graph cache key
+ * and every overlap check follow the format; changing it rebuilds the host
+ * pipeline on the next host call. Other values of `format` are refused with
+ * DIS_ERR_INVALID_ARGUMENT. */
+typedef enum dis_flow_format { DIS_FLOW_F32 = 0, DIS_FLOW_F16 = 1 } dis_flow_format;
+dis_status dis_set_flow_format(dis_ctx* ctx, int format);
+
+/* `count` flow values from src_format to dst_format (dis_flow_format each; no
+ * context, like dis_flow_color; added within ABI v8). f32 -> f16 is the
+ * conversion described above (the very device function the engine's writers
+ * use), f16 -> f32 is exact, equal formats copy. src and dst must not overlap.
+ * Host pointers: synchronous (staged through HIP device `device`). Device
+ * pointers: asynchronous on `stream`; aligned to their element (4 / 2 bytes),
+ * vectorised when the two buffers are equally offset from 16- / 8-byte
+ * boundaries. */
+dis_status dis_flow_convert(const void* src, int src_format, void* dst, int dst_format, size_t count,
+                            dis_mem where, void* stream, int device);
+
 /* One pair: u8 grayscale frames (row stride `stride` bytes, 0 = width) to a
- * full-resolution W x H x 2 float flow, (u,v) interleaved, row-major.
+ * full-resolution W x H x 2 flow, (u,v) interleaved, row-major: floats, or
+ * halves under DIS_FLOW_F16 (`flow` is format-typed, dis_set_flow_format).
  * Replaces R3 + R1 + R2 for one pair (src/main.cpp:135-198). */
 dis_status dis_calc_u8(dis_ctx* ctx, const uint8_t* I0, const uint8_t* I1, size_t stride,
                        float* flow, dis_mem where, void* stream);
 
 /* n pairs in one call: pair k's frames at I0 + k*pair_stride (bytes), its
- * flow at flow + k*W*H*2 floats. n <= max_batch. */
+ * flow at k*W*H*2 values (floats, or halves under DIS_FLOW_F16) after `flow`,
+ * which is format-typed. n <= max_batch. */
 dis_status dis_calc_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const uint8_t* I1,
                              size_t stride, size_t pair_stride, float* flow,
                              dis_mem where, void* stream);
@@ -127,8 +171,8 @@ dis_status dis_calc_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const uint8
  * dis_calc_batch_u8(I1, I0) gives -- bit for bit in DIS_PRECISION_EXACT, and
  * bit for bit in DIS_PRECISION_FMA for the same n and concurrency. Each frame
  * is read and its pyramid built once; the backward pass is the same level loop
- * with the two frames' planes swapped. The two n*W*H*2-float outputs must not
- * overlap. Always enqueued eagerly (never a replayed graph). DIS_MEM_HOST is
+ * with the two frames' planes swapped. The two outputs (format-typed:
+ * n*W*H*2 floats, or halves under DIS_FLOW_F16) must not overlap. Always enqueued eagerly (never a replayed graph). DIS_MEM_HOST is
  * synchronous and stages through device buffers for max_batch pairs that the
  * context allocates on the first such call (DIS_ERR_OUT_OF_MEMORY if that
  * fails); the chunked host pipeline below is not used. After this call
@@ -176,7 +220,10 @@ dis_status dis_calc_bidir_batch_u8(dis_ctx* ctx, int n, const uint8_t* I0, const
  * (DIS_ERR_OUT_OF_MEMORY if that fails); the chunked host pipeline is not
  * used. The context's init planes (a few KB) are allocated by dis_create.
  * dis_flow_to_init is the reduction alone, into the caller's planes (device
- * pointers 8-byte aligned; it touches no context workspace). */
+ * pointers 8-byte aligned; it touches no context workspace). Under
+ * DIS_FLOW_F16 `flow`, a DIS_INIT_FULLRES `init` and dis_flow_to_init's `flow`
+ * are format-typed (halves; device pointers 4-byte aligned); DIS_INIT_COARSE
+ * planes and dis_flow_to_init's output stay float. */
 typedef enum dis_init_kind { DIS_INIT_COARSE = 0, DIS_INIT_FULLRES = 1 } dis_init_kind;
 dis_status dis_init_plane_size(dis_ctx* ctx, int* iw, int* ih);
 dis_status dis_flow_to_init(dis_ctx* ctx, int n, const float* flow, float* init_planes,

@@ -14,6 +14,7 @@
 // Arithmetic is exactly that of the stand-alone kernels in dis_kernels.hip
 // (and of the oracle): same expressions, same order, -ffp-contract=off.
 #include "dis_device.h"
+#include "dis_half.h"
 #include "dis_kernels.h"
 
 #include <type_traits>
@@ -425,6 +426,11 @@ __device__ __forceinline__ void store_flow2(float2* dst, float2 o0, float2 o1)
 {
     *reinterpret_cast<float4*>(dst) = make_float4(o0.x, o0.y, o1.x, o1.y);
 }
+// DIS_FLOW_F16: the same two pixels narrowed, one 8-byte store
+__device__ __forceinline__ void store_flow2(__half2* dst, float2 o0, float2 o1)
+{
+    *reinterpret_cast<half2x2*>(dst) = half2x2{narrow2(o0), narrow2(o1)};
+}
 
 // Output rows of an interior tile at F == 1 (every tap unclamped, every column
 // two-tap, the tile inside W x H). lin_coef then reduces to
@@ -434,7 +440,7 @@ __device__ __forceinline__ void store_flow2(float2* dst, float2 o0, float2 o1)
 // and each source row's horizontal interpolation -- the same expression as
 // the general path, hence the same value -- is formed once and shared by the
 // (up to four) output rows that read it.
-template <int YP, int XP, int SW, int RPT>
+template <int YP, int XP, int SW, int RPT, class OT>
 __device__ __forceinline__ void out_rows_f1(const OutputArgs& a, const float2* dense, int i0, int j0, int px, int py,
                                             int pair)
 {
@@ -457,7 +463,7 @@ __device__ __forceinline__ void out_rows_f1(const OutputArgs& a, const float2* d
             h1[t] = make_float2(sa.x * (1.f - xf1) + sb.x * xf1, sa.y * (1.f - xf1) + sb.y * xf1);
         }
     }
-    float2* dst = a.flow + (size_t)pair * a.W * a.H + (size_t)py * a.W + px;
+    OT* dst = reinterpret_cast<OT*>(a.flow) + (size_t)pair * a.W * a.H + (size_t)py * a.W + px;
 #pragma unroll
     for (int d = 0; d < RPT; ++d) {
         const int t = (d + YP) >> 1;                         // yi - (first source row)
@@ -477,7 +483,9 @@ __device__ __forceinline__ void out_rows_f1(const OutputArgs& a, const float2* d
 //    121-182), 3) F == 0: crop; F >= 1: scale by 2^F, resize, crop.
 // K = ceil(ps / steps) bounds the covering patches per axis, so the gather is
 // an unrolled, predicated K x K loop (no divergent loops).
-template <bool UPSAMPLE, int K, bool kPaper = false>
+// OT is the output's vector type: float2, or __half2 for DIS_FLOW_F16 (the
+// flows narrowed in the stores, dis_half.h; a.flow then points at __half2).
+template <bool UPSAMPLE, int K, bool kPaper = false, class OT = float2>
 __global__ void __launch_bounds__(256) k_output(OutputArgs a)
 {
     constexpr int kTH = kOutTHf<UPSAMPLE>;
@@ -815,10 +823,10 @@ __global__ void __launch_bounds__(256) k_output(OutputArgs a)
             oy + a.pad_top >= 1 && ((xh - 1) >> 1) + 1 <= a.wF - 1 && ((yh - 1) >> 1) + 1 <= a.hF - 1 &&
             xh < a.xmax) {  // uniform: an interior tile
             switch (((a.pad_top - 1) & 1) * 2 + ((a.pad_left - 1) & 1)) {
-                case 0: out_rows_f1<0, 0, kOutSW, RPT>(a, dense, i0, j0, px, py, pair); break;
-                case 1: out_rows_f1<0, 1, kOutSW, RPT>(a, dense, i0, j0, px, py, pair); break;
-                case 2: out_rows_f1<1, 0, kOutSW, RPT>(a, dense, i0, j0, px, py, pair); break;
-                default: out_rows_f1<1, 1, kOutSW, RPT>(a, dense, i0, j0, px, py, pair); break;
+                case 0: out_rows_f1<0, 0, kOutSW, RPT, OT>(a, dense, i0, j0, px, py, pair); break;
+                case 1: out_rows_f1<0, 1, kOutSW, RPT, OT>(a, dense, i0, j0, px, py, pair); break;
+                case 2: out_rows_f1<1, 0, kOutSW, RPT, OT>(a, dense, i0, j0, px, py, pair); break;
+                default: out_rows_f1<1, 1, kOutSW, RPT, OT>(a, dense, i0, j0, px, py, pair); break;
             }
             return;
         }
@@ -863,16 +871,16 @@ __global__ void __launch_bounds__(256) k_output(OutputArgs a)
             o[0] = row[0];
             o[1] = row[1];
         }
-        float2* dst = a.flow + (size_t)pair * a.W * a.H + (size_t)y * a.W + px;
+        OT* dst = reinterpret_cast<OT*>(a.flow) + (size_t)pair * a.W * a.H + (size_t)y * a.W + px;
         if (px + 1 < a.W) {
             if (a.vec_store) {
                 store_flow2(dst, o[0], o[1]);
             } else {
-                dst[0] = o[0];
-                dst[1] = o[1];
+                store_flow1(dst, o[0]);
+                store_flow1(dst + 1, o[1]);
             }
         } else if (px < a.W) {
-            dst[0] = o[0];
+            store_flow1(dst, o[0]);
         }
     }
 }
@@ -884,31 +892,39 @@ bool output_fits(const OutputArgs& a)
     return a.hp == 4 && a.steps >= 2;
 }
 
-template <int K>
+template <int K, class OT>
 static void launch_output_k(const OutputArgs& a, dim3 grid, hipStream_t s, Timing t)
 {
     if (a.paper) {
         if (a.F == 0)
-            DIS_LAUNCH(t, (k_output<false, K, true>), grid, dim3(256), 0, s, a);
+            DIS_LAUNCH(t, (k_output<false, K, true, OT>), grid, dim3(256), 0, s, a);
         else
-            DIS_LAUNCH(t, (k_output<true, K, true>), grid, dim3(256), 0, s, a);
+            DIS_LAUNCH(t, (k_output<true, K, true, OT>), grid, dim3(256), 0, s, a);
     } else if (a.F == 0) {
-        DIS_LAUNCH(t, (k_output<false, K>), grid, dim3(256), 0, s, a);
+        DIS_LAUNCH(t, (k_output<false, K, false, OT>), grid, dim3(256), 0, s, a);
     } else {
-        DIS_LAUNCH(t, (k_output<true, K>), grid, dim3(256), 0, s, a);
+        DIS_LAUNCH(t, (k_output<true, K, false, OT>), grid, dim3(256), 0, s, a);
     }
 }
 
-hipError_t launch_output(const OutputArgs& a, int batch, hipStream_t s, Timing t)
+hipError_t launch_output(const OutputArgs& a, int batch, hipStream_t s, Timing t, int f16)
 {
     if (!output_fits(a)) return hipErrorInvalidValue;
     const int th = a.F == 0 ? kOutTHf<false> : kOutTHf<true>;
     dim3 grid((a.W + kOutTW - 1) / kOutTW, (a.H + th - 1) / th, batch);
     switch ((2 * a.hp + a.steps - 1) / a.steps) {  // K = ceil(ps / steps)
-        case 1: launch_output_k<1>(a, grid, s, t); break;
-        case 2: launch_output_k<2>(a, grid, s, t); break;
-        case 3: launch_output_k<3>(a, grid, s, t); break;
-        case 4: launch_output_k<4>(a, grid, s, t); break;
+#define DIS_CASE(KK)                                        \
+    case KK:                                                \
+        if (f16)                                            \
+            launch_output_k<KK, __half2>(a, grid, s, t);    \
+        else                                                \
+            launch_output_k<KK, float2>(a, grid, s, t);     \
+        break;
+        DIS_CASE(1)
+        DIS_CASE(2)
+        DIS_CASE(3)
+        DIS_CASE(4)
+#undef DIS_CASE
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

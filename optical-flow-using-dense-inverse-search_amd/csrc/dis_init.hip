@@ -28,23 +28,29 @@
 // K <= 5: no LDS; a workgroup is four independent regions and the lanes that
 // hold a finished cell store it.
 //
+// H16 (DIS_FLOW_F16): the flow holds __half2 vectors, widened exactly on load
+// (an interior block's row is two 8-byte loads); everything after the load is
+// the same arithmetic on the same f32 values.
+//
 // k_init_copy is the DIS_INIT_COARSE form: the caller's planes copied into the
 // context's with the same sanitising.
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
+#include "dis_half.h"
 #include "dis_kernels.h"
 
 namespace dis {
 namespace {
 
 struct InitArgs {
-    const float2* flow;  // n W x H fields, pair stride W * H
+    const void* flow;    // n W x H fields of float2 (H16: __half2), pair stride W * H
     float2* plane;       // n iw x ih planes, pair stride iw * ih
     int W, H, Wp, Hp, pl, pt;
     int K;               // halvings (C + 1), 1..kMaxLevels - 1
     int WC, HC, iw, ih;  // level-C size, plane size
-    int vec;             // flow 16-byte aligned, W and pad_left even: float4 loads of interior blocks
+    int vec;             // flow 16-byte aligned (H16: 8-byte), W and pad_left even: two-vector loads of interior blocks
     int rgx, rgy;        // K <= 5: 32 x 32 regions covering iw * 2^K x ih * 2^K
 };
 
@@ -68,11 +74,18 @@ __device__ __forceinline__ float2 box4_clamped(float2 a, float2 b, float2 c, flo
 
 // P_0 at padded-frame pixel (x, y); zero outside the padded frame (only the
 // clamped-away half of an odd last step lies there)
-__device__ __forceinline__ float2 load_px(const InitArgs& a, const float2* __restrict__ F, int x, int y)
+template <bool H16>
+using FlowVec = std::conditional_t<H16, __half2, float2>;
+
+__device__ __forceinline__ float2 load_vec(const float2* p) { return *p; }
+__device__ __forceinline__ float2 load_vec(const __half2* p) { return widen2(*p); }
+
+template <bool H16>
+__device__ __forceinline__ float2 load_px(const InitArgs& a, const FlowVec<H16>* __restrict__ F, int x, int y)
 {
     if (x >= a.Wp || y >= a.Hp) return make_float2(0.0f, 0.0f);
     const int sx = min(max(x - a.pl, 0), a.W - 1), sy = min(max(y - a.pt, 0), a.H - 1);
-    const float2 v = F[(long long)sy * a.W + sx];
+    const float2 v = load_vec(F + (long long)sy * a.W + sx);
     return make_float2(sane(v.x), sane(v.y));
 }
 
@@ -86,7 +99,8 @@ __device__ __forceinline__ float2 shfl_xor2(float2 v, int m)
 // holding a finished cell store it and the return value is unused; K > 5: the
 // region's level-5 value, valid in lane 0. Every lane of the wave must call it
 // (shuffles).
-__device__ __forceinline__ float2 reduce_region(const InitArgs& a, const float2* __restrict__ F,
+template <bool H16>
+__device__ __forceinline__ float2 reduce_region(const InitArgs& a, const FlowVec<H16>* __restrict__ F,
                                                 float2* __restrict__ out, int RX, int RY, int lane)
 {
     const int lx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4);
@@ -99,18 +113,28 @@ __device__ __forceinline__ float2 reduce_region(const InitArgs& a, const float2*
         // interior block: rows of two 16-byte loads (fx even, W even: aligned)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float4* const r = reinterpret_cast<const float4*>(F + (long long)(fy + j) * a.W + fx);
-            const float4 lo = r[0], hi = r[1];
-            p[j][0] = make_float2(sane(lo.x), sane(lo.y));
-            p[j][1] = make_float2(sane(lo.z), sane(lo.w));
-            p[j][2] = make_float2(sane(hi.x), sane(hi.y));
-            p[j][3] = make_float2(sane(hi.z), sane(hi.w));
+            if constexpr (H16) {  // two 8-byte loads
+                const half2x2* const r = reinterpret_cast<const half2x2*>(F + (long long)(fy + j) * a.W + fx);
+                const half2x2 lo = r[0], hi = r[1];
+                const float2 v0 = widen2(lo.a), v1 = widen2(lo.b), v2 = widen2(hi.a), v3 = widen2(hi.b);
+                p[j][0] = make_float2(sane(v0.x), sane(v0.y));
+                p[j][1] = make_float2(sane(v1.x), sane(v1.y));
+                p[j][2] = make_float2(sane(v2.x), sane(v2.y));
+                p[j][3] = make_float2(sane(v3.x), sane(v3.y));
+            } else {
+                const float4* const r = reinterpret_cast<const float4*>(F + (long long)(fy + j) * a.W + fx);
+                const float4 lo = r[0], hi = r[1];
+                p[j][0] = make_float2(sane(lo.x), sane(lo.y));
+                p[j][1] = make_float2(sane(lo.z), sane(lo.w));
+                p[j][2] = make_float2(sane(hi.x), sane(hi.y));
+                p[j][3] = make_float2(sane(hi.z), sane(hi.w));
+            }
         }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) p[j][i] = load_px(a, F, X0 + i, Y0 + j);
+            for (int i = 0; i < 4; ++i) p[j][i] = load_px<H16>(a, F, X0 + i, Y0 + j);
     }
     // level 1 (the last one at K == 1: clamped per cell)
     float2 q[2][2];
@@ -151,18 +175,20 @@ __device__ __forceinline__ float2 reduce_region(const InitArgs& a, const float2*
 }
 
 // K <= 5. grid: (ceil(rgx / 2), ceil(rgy / 2), n); 256 threads = 2 x 2 regions
+template <bool H16>
 __global__ void __launch_bounds__(256) k_flow_to_init_small(InitArgs a)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int rx = blockIdx.x * 2 + (wave & 1), ry = blockIdx.y * 2 + (wave >> 1);
     if (rx >= a.rgx || ry >= a.rgy) return;  // whole wave
     const long long pair = blockIdx.z;
-    reduce_region(a, a.flow + pair * a.W * a.H, a.plane + pair * a.iw * a.ih, rx * 32, ry * 32, lane);
+    reduce_region<H16>(a, static_cast<const FlowVec<H16>*>(a.flow) + pair * a.W * a.H, a.plane + pair * a.iw * a.ih,
+                       rx * 32, ry * 32, lane);
 }
 
 // K >= 6. grid: (iw, ih, n), one 2^K tile per workgroup; NW = 4 (K == 6) or 16
 // waves, wave w the tile's Morton sub-square w of side 2^(K - j), 4^j = NW
-template <int NW>
+template <int NW, bool H16>
 __global__ void __launch_bounds__(64 * NW) k_flow_to_init(InitArgs a)
 {
     constexpr int J = NW == 4 ? 1 : 2;
@@ -171,7 +197,7 @@ __global__ void __launch_bounds__(64 * NW) k_flow_to_init(InitArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int ox = blockIdx.x, oy = blockIdx.y;
     const long long pair = blockIdx.z;
-    const float2* const F = a.flow + pair * a.W * a.H;
+    const FlowVec<H16>* const F = static_cast<const FlowVec<H16>*>(a.flow) + pair * a.W * a.H;
     const int K = a.K, S = 1 << (K - J);
     // Morton position of the wave's sub-square in the tile
     const int sx = J == 1 ? (wave & 1) : ((wave & 1) | ((wave >> 1) & 2));
@@ -188,7 +214,7 @@ __global__ void __launch_bounds__(64 * NW) k_flow_to_init(InitArgs a)
                 rx |= ((i >> (2 * b)) & 1) << b;
                 ry |= ((i >> (2 * b + 1)) & 1) << b;
             }
-            float2 cur = reduce_region(a, F, nullptr, SX + 32 * rx, SY + 32 * ry, lane);
+            float2 cur = reduce_region<H16>(a, F, nullptr, SX + 32 * rx, SY + 32 * ry, lane);
             if (lane == 0) {
                 // binary-counter carries: four finished siblings make their parent
                 int lvl = 0, idx = i;
@@ -235,10 +261,11 @@ void init_plane_size(const Geometry& g, int* iw, int* ih)
     *ih = (g.lv[g.C].H + 1) / 2;
 }
 
-hipError_t launch_flow_to_init(const float* flow, float* planes, int n, const Geometry& g, hipStream_t s, Timing t)
+hipError_t launch_flow_to_init(const float* flow, float* planes, int n, const Geometry& g, hipStream_t s, Timing t,
+                               int f16)
 {
     InitArgs a{};
-    a.flow = reinterpret_cast<const float2*>(flow);
+    a.flow = flow;
     a.plane = reinterpret_cast<float2*>(planes);
     a.W = g.W;
     a.H = g.H;
@@ -250,21 +277,28 @@ hipError_t launch_flow_to_init(const float* flow, float* planes, int n, const Ge
     a.WC = g.lv[g.C].W;
     a.HC = g.lv[g.C].H;
     init_plane_size(g, &a.iw, &a.ih);
-    a.vec = ((reinterpret_cast<uintptr_t>(flow) & 15) == 0 && (g.W & 1) == 0 && (g.pad_left & 1) == 0) ? 1 : 0;
+    a.vec = ((reinterpret_cast<uintptr_t>(flow) & (f16 ? 7 : 15)) == 0 && (g.W & 1) == 0 && (g.pad_left & 1) == 0) ? 1 : 0;
     if (a.K < 1 || a.K >= kMaxLevels || n < 1 || n > 65535) return hipErrorInvalidValue;
     if (a.K <= 5) {
         a.rgx = (int)((((long long)a.iw << a.K) + 31) / 32);
         a.rgy = (int)((((long long)a.ih << a.K) + 31) / 32);
         const dim3 grid((a.rgx + 1) / 2, (a.rgy + 1) / 2, n);
         if (grid.y > 65535) return hipErrorInvalidValue;
-        DIS_LAUNCH(t, k_flow_to_init_small, grid, dim3(256), 0, s, a);
+        if (f16)
+            DIS_LAUNCH(t, k_flow_to_init_small<true>, grid, dim3(256), 0, s, a);
+        else
+            DIS_LAUNCH(t, k_flow_to_init_small<false>, grid, dim3(256), 0, s, a);
     } else {
         const dim3 grid(a.iw, a.ih, n);
         if (grid.y > 65535) return hipErrorInvalidValue;
-        if (a.K == 6)
-            DIS_LAUNCH(t, k_flow_to_init<4>, grid, dim3(256), 0, s, a);
+        if (a.K == 6 && f16)
+            DIS_LAUNCH(t, (k_flow_to_init<4, true>), grid, dim3(256), 0, s, a);
+        else if (a.K == 6)
+            DIS_LAUNCH(t, (k_flow_to_init<4, false>), grid, dim3(256), 0, s, a);
+        else if (f16)
+            DIS_LAUNCH(t, (k_flow_to_init<16, true>), grid, dim3(1024), 0, s, a);
         else
-            DIS_LAUNCH(t, k_flow_to_init<16>, grid, dim3(1024), 0, s, a);
+            DIS_LAUNCH(t, (k_flow_to_init<16, false>), grid, dim3(1024), 0, s, a);
     }
     return hipGetLastError();
 }

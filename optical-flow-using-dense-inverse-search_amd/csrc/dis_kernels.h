@@ -132,7 +132,7 @@ struct OutputArgs {
     long long u_stride;
     int W, H, wF, hF, F, pad_left, pad_top, xmax;
     int npw, nph, offw, offh, steps, hp;
-    int vec_store;     // output base is 16-byte aligned and W even
+    int vec_store;     // W even and the output base 16-byte aligned (f16 output: 8-byte aligned)
     float sc;
     // paper mode: votes weighted by 1/max(1, |I1(x+u) - I0(x)|) on level F
     int paper;
@@ -147,7 +147,9 @@ hipError_t launch_pyramid(const PyramidArgs& a, int batch, hipStream_t s, Timing
 bool pyramid2_fits(const PyramidArgs& a);
 hipError_t launch_pyramid2(const PyramidArgs& a, int batch, hipStream_t s, Timing t = {});
 bool output_fits(const OutputArgs& a);
-hipError_t launch_output(const OutputArgs& a, int batch, hipStream_t s, Timing t = {});
+// f16 != 0 (here and in launch_upsample): a.flow points at __half2 vectors
+// (DIS_FLOW_F16), written by the kernels' __half2 instantiations
+hipError_t launch_output(const OutputArgs& a, int batch, hipStream_t s, Timing t = {}, int f16 = 0);
 hipError_t launch_level0(const uint8_t* I0, const uint8_t* I1, size_t stride, size_t pair_stride,
                          const Geometry& g, float* img0, float* img1, int batch, hipStream_t s);
 hipError_t launch_down2(const Geometry& g, int l, float* img0, float* img1, int batch, hipStream_t s);
@@ -161,7 +163,7 @@ hipError_t launch_search8(const Search8Args& a, int batch, hipStream_t s, Timing
 // one wave64 per patch (dis_search_wave.hip; lanes_per_patch 64, variant 6)
 hipError_t launch_search_wave(const Search8Args& a, int batch, hipStream_t s, Timing t = {});
 hipError_t launch_densify(const DensifyArgs& a, int batch, hipStream_t s);
-hipError_t launch_upsample(const UpsampleArgs& a, int batch, hipStream_t s);
+hipError_t launch_upsample(const UpsampleArgs& a, int batch, hipStream_t s, int f16 = 0);
 
 // Middlebury colour coding of n W x H (u,v) fields into BGR u8 (dis_color.hip);
 // maxbits: 32 * n device uints of scratch.
@@ -182,10 +184,15 @@ hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int 
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in
 // one launch; launch_init_copy is the sanitising copy of `count` floats of
 // caller-made planes.
+// f16 != 0: `flow` holds __half2 vectors (DIS_FLOW_F16), widened on load.
 void init_plane_size(const Geometry& g, int* iw, int* ih);
 hipError_t launch_flow_to_init(const float* flow, float* planes, int n, const Geometry& g, hipStream_t s,
-                               Timing t = {});
+                               Timing t = {}, int f16 = 0);
 hipError_t launch_init_copy(const float* src, float* dst, long long count, hipStream_t s, Timing t = {});
+
+// dis_flow_convert's kernel (dis_convert.hip): `count` values from src_format
+// to the other format (DIS_FLOW_F32 / DIS_FLOW_F16; the formats differ).
+hipError_t launch_flow_convert(const void* src, int src_format, void* dst, size_t count, hipStream_t s);
 
 // Variational refinement of one level's dense flow (dis_varref.hip).
 constexpr int kVarRefPlanes = 8;   // per-pair workspace planes

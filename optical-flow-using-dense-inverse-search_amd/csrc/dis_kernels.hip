@@ -9,6 +9,7 @@
 // launch covers a whole batch of frame pairs (coarse levels have too few
 // patches per pair to fill 256 CUs otherwise).
 #include "dis_device.h"
+#include "dis_half.h"
 #include "dis_kernels.h"
 
 namespace dis {
@@ -421,6 +422,9 @@ __device__ __forceinline__ Coef lin_coef(int d, int n_src, double scale)
     return c;
 }
 
+// OT: the output's vector type, float2 or __half2 (DIS_FLOW_F16: narrowed in
+// the store, dis_half.h; one 4-byte store per pixel)
+template <class OT>
 __global__ void __launch_bounds__(256) k_upsample_crop(UpsampleArgs a)
 {
     const int x = blockIdx.x * 64 + threadIdx.x;
@@ -428,10 +432,10 @@ __global__ void __launch_bounds__(256) k_upsample_crop(UpsampleArgs a)
     const int pair = blockIdx.z;
     if (x >= a.W || y >= a.H) return;
     const float2* S = a.dense + (size_t)pair * a.dense_stride;
-    float2* out = a.flow + (size_t)pair * a.W * a.H;
+    OT* out = reinterpret_cast<OT*>(a.flow) + (size_t)pair * a.W * a.H;
     const int xx = x + a.pad_left, yy = y + a.pad_top;
     if (a.F == 0) {
-        out[(size_t)y * a.W + x] = S[(size_t)yy * a.wF + xx];
+        store_flow1(out + (size_t)y * a.W + x, S[(size_t)yy * a.wF + xx]);
         return;
     }
     const float sc = a.sc;
@@ -456,7 +460,7 @@ __global__ void __launch_bounds__(256) k_upsample_crop(UpsampleArgs a)
         }
     }
     const float b0 = 1.f - cy.f, b1 = cy.f;
-    out[(size_t)y * a.W + x] = make_float2(h[0][0] * b0 + h[1][0] * b1, h[0][1] * b0 + h[1][1] * b1);
+    store_flow1(out + (size_t)y * a.W + x, make_float2(h[0][0] * b0 + h[1][0] * b1, h[0][1] * b0 + h[1][1] * b1));
 }
 
 // ---------------------------------------------------------------------------
@@ -519,9 +523,12 @@ hipError_t launch_densify(const DensifyArgs& a, int batch, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_upsample(const UpsampleArgs& a, int batch, hipStream_t s)
+hipError_t launch_upsample(const UpsampleArgs& a, int batch, hipStream_t s, int f16)
 {
-    hipLaunchKernelGGL(k_upsample_crop, grid2d(a.W, a.H, batch), dim3(64, 4), 0, s, a);
+    if (f16)
+        hipLaunchKernelGGL(k_upsample_crop<__half2>, grid2d(a.W, a.H, batch), dim3(64, 4), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_upsample_crop<float2>, grid2d(a.W, a.H, batch), dim3(64, 4), 0, s, a);
     return hipGetLastError();
 }
 

@@ -141,9 +141,10 @@ constexpr size_t kFbCounters = dis::kMaxLevels;
 // 4, host-frame path).
 struct HostPipe {
     int chunk = 0;
+    int format = 0;                   // flow format the output slots were sized for
     size_t frame = 0;                 // bytes of one frame (W * H)
     uint8_t* din[2] = {};             // device: chunk I0 frames, then chunk I1 frames
-    float2* dout[2] = {};             // device: chunk flows
+    float2* dout[2] = {};             // device: chunk flows (format-typed)
     hipStream_t up = nullptr, down = nullptr;
     hipEvent_t up_done[2] = {}, comp_done[2] = {}, down_done[2] = {};
     bool comp_pending[2] = {}, down_pending[2] = {};
@@ -242,6 +243,15 @@ struct dis_ctx {
     static constexpr int kMaxSub = 8;
     int nsub = 2;                        // sub-batch streams per calc (dis_set_concurrency)
     int precision = 0;                   // dis_set_precision: DIS_PRECISION_EXACT / _FMA
+    int flow_format = 0;                 // dis_set_flow_format: DIS_FLOW_F32 / _F16
+    bool f16() const { return flow_format == DIS_FLOW_F16; }
+    // bytes of one (u, v) vector of a full-resolution flow in the context's format
+    size_t vec_bytes() const { return f16() ? 2 * sizeof(uint16_t) : sizeof(float2); }
+    // `pairs` flows after a format-typed flow pointer
+    float2* flow_at(float2* flow, size_t pairs) const
+    {
+        return reinterpret_cast<float2*>(reinterpret_cast<char*>(flow) + pairs * g.W * g.H * vec_bytes());
+    }
     hipStream_t sub[kMaxSub] = {};
     hipEvent_t fork = nullptr;
     // end of the previous call's work on its stream: every call first orders
@@ -279,7 +289,7 @@ struct dis_ctx {
         hipEvent_t last = nullptr;  // recorded after this exec's latest launch
         bool launched = false;
         unsigned long long used = 0;  // LRU clock
-        int n = -1, nsub = -1, precision = -1, variant = -1;
+        int n = -1, nsub = -1, precision = -1, variant = -1, format = -1;
         int subs = 1;  // sub-batches the captured call ran (last_nsub on replay)
         const void *i0 = nullptr, *i1 = nullptr;
         void* flow = nullptr;
@@ -781,7 +791,8 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
         o.offh = LF.offh;
         o.steps = LF.steps;
         o.hp = g.ps / 2;
-        o.vec_store = ((reinterpret_cast<uintptr_t>(flow) & 15) == 0 && (g.W & 1) == 0) ? 1 : 0;
+        // two pixels per store: 16 bytes of floats, 8 bytes of halves
+        o.vec_store = ((reinterpret_cast<uintptr_t>(flow) & (c->f16() ? 7 : 15)) == 0 && (g.W & 1) == 0) ? 1 : 0;
         o.sc = std::pow(2.0f, (float)g.F);
         o.paper = paper ? 1 : 0;
         o.img0 = img0 + LF.plane_off;
@@ -790,7 +801,7 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
         fused_out = dis::output_fits(o) && !vr;  // refined: the finest dense field exists
     }
     if (fused_out) {
-        DIS_HIP(dis::launch_output(o, n, s, timing(c, 3)));
+        DIS_HIP(dis::launch_output(o, n, s, timing(c, 3), c->f16()));
     } else {
         if (fast && !c->debug && !vr)  // the level loop skipped the finest densify: do it here
             DIS_HIP(dis::launch_densify(densify_args(c, g.F, img0, img1, pu, dense), n, s));
@@ -809,7 +820,7 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
         u.sc = std::pow(2.0f, (float)g.F);
         u.inv_sc = 1.0 / (double)u.sc;
         u.xmax = upsample_xmax(g);
-        DIS_HIP(dis::launch_upsample(u, n, s));
+        DIS_HIP(dis::launch_upsample(u, n, s, c->f16()));
     }
     return DIS_OK;
 }
@@ -877,7 +888,6 @@ dis_status run_batches(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, 
     }
     auto stream_of = [&](int x) { return x == 0 ? s : c->sub[x - 1]; };
     auto event_of = [&](int e) { return e == 0 ? c->fork : c->join[e - 1]; };
-    const size_t fpp = (size_t)c->g.W * c->g.H;  // float2 per output pair
     for (const dis::PlanOp& o : plan) {
         if (o.kind == dis::kOpRecord) {
             DIS_HIP(hipEventRecord(event_of(o.event), stream_of(o.stream)));
@@ -897,7 +907,7 @@ dis_status run_batches(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, 
             const int dir = (size_t)o.stage >= nfw ? 1 : 0;
             StageRange range(st, k);
             dis_status r = run_batch(c, k, b - a, a, I0 + (size_t)a * pair_stride, I1 + (size_t)a * pair_stride,
-                                     stride, pair_stride, (dir ? flow_bw : flow) + (size_t)a * fpp,
+                                     stride, pair_stride, c->flow_at(dir ? flow_bw : flow, (size_t)a),
                                      stream_of(o.stream), st, dir);
             if (r != DIS_OK) return r;
         }
@@ -925,7 +935,7 @@ dis_status run_batches_graph(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
     auto key_is = [&](const dis_ctx::MainGraph& G) {
         return G.exec && G.n == n && G.i0 == I0 && G.i1 == I1 && G.flow == flow && G.stride == stride &&
                G.pair_stride == pair_stride && G.nsub == c->nsub && G.precision == c->precision &&
-               G.variant == c->variant;
+               G.variant == c->variant && G.format == c->flow_format;
     };
     dis_ctx::MainGraph* G = nullptr;
     for (auto& e : c->mg)
@@ -1018,6 +1028,7 @@ dis_status run_batches_graph(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
         G->nsub = c->nsub;
         G->precision = c->precision;
         G->variant = c->variant;
+        G->format = c->flow_format;  // (a graph holds its kernels: never replayed for the other store type)
         G->subs = c->last_nsub;
     }
     G->used = ++c->graph_clock;
@@ -1060,25 +1071,26 @@ bool host_pinned(const void* p, size_t bytes)
 
 // Device slots, streams and the download thread of the host-frame path, made
 // on the first host call (device-resident callers never pay for them).
-// chunk = 0: about 64 MB of flow per chunk (4 pairs at 1920 x 1080); debug mode
-// keeps the whole batch in one chunk (the stage dumps read the last call's
-// pairs).
+// chunk = 0: about 64 MB of flow per chunk (4 pairs at 1920 x 1080, 8 of f16
+// flow); debug mode keeps the whole batch in one chunk (the stage dumps read
+// the last call's pairs). A changed chunk or flow format rebuilds the pipe.
 dis_status host_pipe_init(dis_ctx* c, int n)
 {
     const size_t frame = (size_t)c->g.W * c->g.H;
     int chunk = c->host_chunk > 0 ? c->host_chunk
-                                  : (int)std::max<size_t>(1, (size_t(64) << 20) / (frame * sizeof(float2)));
+                                  : (int)std::max<size_t>(1, (size_t(64) << 20) / (frame * c->vec_bytes()));
     if (c->debug) chunk = std::max(chunk, n);
     chunk = std::min(chunk, c->max_batch);
-    if (c->hp && c->hp->chunk == chunk) return DIS_OK;
+    if (c->hp && c->hp->chunk == chunk && c->hp->format == c->flow_format) return DIS_OK;
     c->hp.reset();
     auto hp = std::make_unique<HostPipe>();
     hp->chunk = chunk;
+    hp->format = c->flow_format;
     hp->frame = frame;
     hp->device = c->device;
     for (int s = 0; s < 2; ++s) {
         if (hipMalloc(&hp->din[s], 2 * frame * chunk) != hipSuccess ||
-            hipMalloc(&hp->dout[s], sizeof(float2) * frame * chunk) != hipSuccess)
+            hipMalloc(&hp->dout[s], c->vec_bytes() * frame * chunk) != hipSuccess)
             return fail(DIS_ERR_OUT_OF_MEMORY, "host-path device slot allocation failed");
         DIS_HIP(hipEventCreateWithFlags(&hp->up_done[s], hipEventDisableTiming));
         DIS_HIP(hipEventCreateWithFlags(&hp->comp_done[s], hipEventDisableTiming));
@@ -1109,7 +1121,7 @@ dis_status calc_host(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, si
     if (st != DIS_OK) return st;
     HostPipe& P = *c->hp;
     const int W = c->g.W, H = c->g.H, chunk = P.chunk;
-    const size_t fr = P.frame, fb = fr * sizeof(float2);
+    const size_t fr = P.frame, fb = fr * c->vec_bytes();  // bytes of one frame, of one flow
     const size_t in_span = (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W;
     const bool pin_in = host_pinned(I0, in_span) && host_pinned(I1, in_span);
     const bool pin_out = host_pinned(flow, fb * n);
@@ -1492,6 +1504,8 @@ dis_status dis_calc_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
     if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
     if (pair_stride == 0) pair_stride = stride * H;
     if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
+    if (where == DIS_MEM_DEVICE && c->f16() && (reinterpret_cast<uintptr_t>(flow) & 3))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "DIS_FLOW_F16: flow must be 4-byte aligned");
     DIS_HIP(hipSetDevice(c->device));
     if (where == DIS_MEM_DEVICE) {
         return run_batches_graph(c, n, I0, I1, stride, pair_stride, reinterpret_cast<float2*>(flow),
@@ -1519,11 +1533,13 @@ dis_status dis_calc_bidir_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const u
     if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
     if (pair_stride == 0) pair_stride = stride * H;
     if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
-    const size_t fpp = (size_t)W * H;  // float2 per pair
+    const size_t fpp = (size_t)W * H;  // (u, v) vectors per pair
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(flow_fw), b0 = reinterpret_cast<uintptr_t>(flow_bw);
-    const size_t fbytes = sizeof(float2) * fpp * (size_t)n;
+    const size_t fbytes = c->vec_bytes() * fpp * (size_t)n;  // in the context's flow format
     if (a0 < b0 + fbytes && b0 < a0 + fbytes)
         return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
+    if (where == DIS_MEM_DEVICE && c->f16() && ((a0 | b0) & 3))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "DIS_FLOW_F16: flow_fw and flow_bw must be 4-byte aligned");
     DIS_HIP(hipSetDevice(c->device));
     if (where == DIS_MEM_DEVICE) {
         std::lock_guard<std::mutex> lock(pool_mutex(c->device));  // eager enqueue onto the pooled streams
@@ -1532,7 +1548,8 @@ dis_status dis_calc_bidir_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const u
     }
     // host memory: synchronous, staged through device buffers for max_batch
     // pairs made on the first such call (the chunked pipeline of
-    // dis_calc_batch_u8 is not used here)
+    // dis_calc_batch_u8 is not used here); the output staging is sized for
+    // float flows and serves either format
     const size_t B = (size_t)c->max_batch;
     if (!c->bd_in || !c->bd_out) {
         if ((!c->bd_in && hipMalloc(&c->bd_in, 2 * fpp * B) != hipSuccess) ||
@@ -1583,12 +1600,13 @@ dis_status dis_flow_to_init(dis_ctx* c, int n, const float* flow, float* init_pl
     DIS_HIP(hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (where == DIS_MEM_DEVICE) {
-        if (reinterpret_cast<uintptr_t>(flow) & 7 || reinterpret_cast<uintptr_t>(init_planes) & 7)
-            return fail(DIS_ERR_INVALID_ARGUMENT, "flow and init_planes must be 8-byte aligned");
-        DIS_HIP(dis::launch_flow_to_init(flow, init_planes, n, c->g, s));
+        if (reinterpret_cast<uintptr_t>(flow) & (c->f16() ? 3 : 7) || reinterpret_cast<uintptr_t>(init_planes) & 7)
+            return fail(DIS_ERR_INVALID_ARGUMENT,
+                        "flow and init_planes must be 8-byte aligned (a DIS_FLOW_F16 flow: 4-byte)");
+        DIS_HIP(dis::launch_flow_to_init(flow, init_planes, n, c->g, s, {}, c->f16()));
         return DIS_OK;
     }
-    const size_t fbytes = sizeof(float2) * (size_t)c->g.W * c->g.H * n;
+    const size_t fbytes = c->vec_bytes() * (size_t)c->g.W * c->g.H * n;  // in the context's flow format
     const size_t pbytes = sizeof(float2) * (size_t)c->iw * c->ih * n;
     float *dflow = nullptr, *dplanes = nullptr;
     dis_status rc = DIS_OK;
@@ -1596,7 +1614,7 @@ dis_status dis_flow_to_init(dis_ctx* c, int n, const float* flow, float* init_pl
         (void)hipGetLastError();
         rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
     } else if (hipMemcpyAsync(dflow, flow, fbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_to_init(dflow, dplanes, n, c->g, s) != hipSuccess ||
+               dis::launch_flow_to_init(dflow, dplanes, n, c->g, s, {}, c->f16()) != hipSuccess ||
                hipMemcpyAsync(init_planes, dplanes, pbytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
                hipStreamSynchronize(s) != hipSuccess) {
         rc = fail(DIS_ERR_DEVICE, "flow to init plane reduction failed");
@@ -1629,9 +1647,9 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
     if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
     if (pair_stride == 0) pair_stride = stride * H;
     if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
-    const size_t fpp = (size_t)W * H;                 // float2 per flow
+    const size_t fpp = (size_t)W * H;                 // (u, v) vectors per flow
     const size_t ipp = (size_t)c->iw * c->ih;         // float2 per init plane
-    const size_t fbytes = sizeof(float2) * fpp * (size_t)n;
+    const size_t fbytes = c->vec_bytes() * fpp * (size_t)n;  // in the context's flow format (FULLRES init too)
     const size_t ibytes = init_kind == DIS_INIT_FULLRES ? fbytes : sizeof(float2) * ipp * (size_t)n;
     const size_t frame_bytes = (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W;
     if (const char* why = dis::check_init_aliasing(reinterpret_cast<uintptr_t>(init), ibytes,
@@ -1639,8 +1657,11 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
                                                    reinterpret_cast<uintptr_t>(I0), reinterpret_cast<uintptr_t>(I1),
                                                    frame_bytes))
         return fail(DIS_ERR_INVALID_ARGUMENT, why);
-    if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(init) & 7))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "init must be 8-byte aligned");
+    const bool init_f16 = c->f16() && init_kind == DIS_INIT_FULLRES;
+    if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(init) & (init_f16 ? 3 : 7)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "init must be 8-byte aligned (a DIS_FLOW_F16 flow: 4-byte)");
+    if (where == DIS_MEM_DEVICE && c->f16() && (reinterpret_cast<uintptr_t>(flow) & 3))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "DIS_FLOW_F16: flow must be 4-byte aligned");
     DIS_HIP(hipSetDevice(c->device));
     // Fill the planes on `s`, then run the chain on `s`: every sub-batch stream
     // forks from `s` after the fill, so the planes are complete -- and `init`
@@ -1650,7 +1671,8 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
                        hipStream_t s) -> dis_status {
         if (c->needs_wait(s)) DIS_HIP(hipStreamWaitEvent(s, c->done, 0));  // the planes are workspace
         if (init_kind == DIS_INIT_FULLRES)
-            DIS_HIP(dis::launch_flow_to_init(in, reinterpret_cast<float*>(c->init), n, c->g, s, timing(c, 6)));
+            DIS_HIP(dis::launch_flow_to_init(in, reinterpret_cast<float*>(c->init), n, c->g, s, timing(c, 6),
+                                             c->f16()));
         else
             DIS_HIP(dis::launch_init_copy(in, reinterpret_cast<float*>(c->init), (long long)(2 * ipp) * n, s,
                                           timing(c, 6)));
@@ -1665,7 +1687,8 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
                        reinterpret_cast<hipStream_t>(stream));
     // host memory: synchronous, staged through device buffers for max_batch
     // pairs made on the first such call (the chunked pipeline of
-    // dis_calc_batch_u8 is not used here)
+    // dis_calc_batch_u8 is not used here); the flow and init staging is sized
+    // for float flows and serves either format
     const size_t B = (size_t)c->max_batch;
     if (!c->wi_in || !c->wi_out) {
         if ((!c->wi_in && hipMalloc(&c->wi_in, 2 * fpp * B) != hipSuccess) ||
@@ -1771,6 +1794,17 @@ dis_status dis_set_precision(dis_ctx* c, int mode)
     if (mode != DIS_PRECISION_EXACT && mode != DIS_PRECISION_FMA)
         return fail(DIS_ERR_INVALID_ARGUMENT, "precision must be DIS_PRECISION_EXACT or DIS_PRECISION_FMA");
     c->precision = mode;
+    return DIS_OK;
+}
+
+dis_status dis_set_flow_format(dis_ctx* c, int format)
+{
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (format != DIS_FLOW_F32 && format != DIS_FLOW_F16)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    // (the host pipeline's slots and the graph cache follow at the next call:
+    // both compare the format they were made for)
+    c->flow_format = format;
     return DIS_OK;
 }
 
@@ -2069,6 +2103,53 @@ dis_status dis_flow_color(const float* flow, int n, int width, int height, float
     hipFree(dflow);
     hipFree(dbgr);
     hipFree(maxbits);
+    return rc;
+}
+
+dis_status dis_flow_convert(const void* src, int src_format, void* dst, int dst_format, size_t count, dis_mem where,
+                            void* stream, int device)
+{
+    if (!src || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((src_format != DIS_FLOW_F32 && src_format != DIS_FLOW_F16) ||
+        (dst_format != DIS_FLOW_F32 && dst_format != DIS_FLOW_F16))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "formats must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    const size_t ssz = src_format == DIS_FLOW_F16 ? 2 : 4, dsz = dst_format == DIS_FLOW_F16 ? 2 : 4;
+    if (count > (size_t(1) << 40)) return fail(DIS_ERR_INVALID_ARGUMENT, "count too large");
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(src), da = reinterpret_cast<uintptr_t>(dst);
+    if (sa < da + count * dsz && da < sa + count * ssz) return fail(DIS_ERR_INVALID_ARGUMENT, "src and dst overlap");
+    if (where == DIS_MEM_DEVICE && ((sa & (ssz - 1)) || (da & (dsz - 1))))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers must be aligned to their element (4 / 2 bytes)");
+    if (!count) return DIS_OK;
+    if (where == DIS_MEM_HOST && src_format == dst_format) {  // a host copy needs no device
+        std::memcpy(dst, src, count * ssz);
+        return DIS_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    DIS_HIP(hipSetDevice(device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (where == DIS_MEM_DEVICE) {
+        if (src_format == dst_format)
+            DIS_HIP(hipMemcpyAsync(dst, src, count * ssz, hipMemcpyDeviceToDevice, s));
+        else
+            DIS_HIP(dis::launch_flow_convert(src, src_format, dst, count, s));
+        return DIS_OK;
+    }
+    void *dsrc = nullptr, *ddst = nullptr;
+    dis_status rc = DIS_OK;
+    if (hipMalloc(&dsrc, count * ssz) != hipSuccess || hipMalloc(&ddst, count * dsz) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
+    } else if (hipMemcpyAsync(dsrc, src, count * ssz, hipMemcpyHostToDevice, s) != hipSuccess ||
+               dis::launch_flow_convert(dsrc, src_format, ddst, count, s) != hipSuccess ||
+               hipMemcpyAsync(dst, ddst, count * dsz, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               hipStreamSynchronize(s) != hipSuccess) {
+        rc = fail(DIS_ERR_DEVICE, "flow conversion failed");
+    }
+    hipFree(dsrc);
+    hipFree(ddst);
     return rc;
 }
 

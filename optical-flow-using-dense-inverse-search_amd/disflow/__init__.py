@@ -52,6 +52,24 @@ KERNEL_PYRAMID, KERNEL_SEARCH, KERNEL_SEARCH_FINEST, KERNEL_DENSIFY, KERNEL_VR_L
 KERNEL_INIT = 6  # the init-plane launch of a warm-started call
 
 INIT_COARSE, INIT_FULLRES = 0, 1
+
+FLOW_F32, FLOW_F16 = 0, 1  # dis_flow_format
+
+
+def _flow_format(dtype) -> int:
+    """dis_flow_format of a flow dtype (np.float32 / np.float16); ValueError for any other."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt == np.float32:
+        return FLOW_F32
+    if dt == np.float16:
+        return FLOW_F16
+    raise ValueError(f"flow dtype must be float32 or float16, not {dtype!r}")
+
+
+_FLOW_DTYPES = {FLOW_F32: np.dtype(np.float32), FLOW_F16: np.dtype(np.float16)}
 _INIT_KINDS = {"coarse": INIT_COARSE, "fullres": INIT_FULLRES, INIT_COARSE: INIT_COARSE, INIT_FULLRES: INIT_FULLRES}
 
 # Every symbol include/dis_abi.h declares (checked by tests/test_abi.py).
@@ -65,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "dis_host_alloc", "dis_host_free", "dis_batch_stream_plan", "dis_check_stream_plan",
     "dis_calc_bidir_batch_u8", "dis_flow_consistency",
     "dis_init_plane_size", "dis_flow_to_init", "dis_calc_batch_init_u8",
+    "dis_set_flow_format", "dis_flow_convert",
 )
 
 
@@ -181,6 +200,9 @@ def lib() -> ctypes.CDLL:
             L.dis_init_plane_size.argtypes = [V, P(I), P(I)]
             L.dis_flow_to_init.argtypes = [V, I, V, V, I, V]
             L.dis_calc_batch_init_u8.argtypes = [V, I, V, V, Z, Z, V, I, V, I, V]
+        if hasattr(L, "dis_set_flow_format"):  # (added within v8)
+            L.dis_set_flow_format.argtypes = [V, I]
+            L.dis_flow_convert.argtypes = [V, I, V, I, Z, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -274,6 +296,26 @@ def flow_consistency_device(fw_ptr: int, bw_ptr: int, n: int, width: int, height
                                       err_ptr or None, MEM_DEVICE, stream or None, device))
 
 
+def flow_convert(array: np.ndarray, dtype, device: int = 0) -> np.ndarray:
+    """dis_flow_convert on a host array: float32 <-> float16 flow values (any
+    shape) on the GPU. float32 -> float16 is the engine's own narrowing (round
+    to nearest even, subnormals kept, |v| >= 65520 -> +-inf); float16 -> float32
+    is exact; equal dtypes copy."""
+    src_format, dst_format = _flow_format(np.asarray(array).dtype), _flow_format(dtype)
+    a = np.ascontiguousarray(array)
+    out = np.empty(a.shape, _FLOW_DTYPES[dst_format])
+    if a.size:
+        _check(lib().dis_flow_convert(_ptr(a), src_format, _ptr(out), dst_format, a.size, MEM_HOST, None, device))
+    return out
+
+
+def flow_convert_device(src_ptr: int, src_dtype, dst_ptr: int, dst_dtype, count: int, stream: int = 0,
+                        device: int = 0) -> None:
+    """dis_flow_convert on raw device pointers (`count` values), asynchronous on `stream`."""
+    _check(lib().dis_flow_convert(src_ptr, _flow_format(src_dtype), dst_ptr, _flow_format(dst_dtype), count,
+                                  MEM_DEVICE, stream or None, device))
+
+
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
     """Read a Middlebury .flo file (src/IO_flow.cpp:10-53) -> (H, W, channels) float32."""
     w, h = ctypes.c_int(), ctypes.c_int()
@@ -322,15 +364,29 @@ def synth_pair(seed: int, width: int, height: int, with_gt: bool = False):
 class DenseInverseSearch:
     """One device context for W x H pairs (dis_create / dis_destroy)."""
 
-    def __init__(self, params, width: int, height: int, max_batch: int = 1, device: int = 0):
+    flow_dtype = np.dtype(np.float32)  # the engine's flow format (set_flow_format)
+
+    def __init__(self, params, width: int, height: int, max_batch: int = 1, device: int = 0,
+                 flow_dtype=np.float32):
+        """flow_dtype: np.float32 (default) or np.float16 -- the format of every
+        full-resolution flow the engine writes and reads (dis_set_flow_format)."""
+        self._ctx = ctypes.c_void_p()  # (close() works after a failed constructor)
+        fmt = _flow_format(flow_dtype)  # raises before any device call
         if isinstance(params, (Preset, int)) and not isinstance(params, Params):
             params = preset_params(Preset(params), width, height)
         self.params = params
         self.width, self.height, self.max_batch = width, height, max_batch
         self.device = device
-        self._ctx = ctypes.c_void_p()
         _check(lib().dis_create(ctypes.byref(self._ctx), ctypes.byref(params._c()), width, height,
                                 max_batch, device))
+        if fmt != FLOW_F32:
+            self.set_flow_format(flow_dtype)
+
+    def set_flow_format(self, flow_dtype) -> None:
+        """dis_set_flow_format: np.float32 or np.float16 flows from the next call on."""
+        fmt = _flow_format(flow_dtype)
+        _check(lib().dis_set_flow_format(self._ctx, fmt))
+        self.flow_dtype = _FLOW_DTYPES[fmt]
 
     def close(self) -> None:
         if self._ctx:
@@ -358,11 +414,18 @@ class DenseInverseSearch:
         return (hc + 1) // 2, (wc + 1) // 2
 
     def _check_init(self, init, init_kind, n: int):
-        """Validate an init array for n pairs -> (contiguous float32 array, kind)."""
+        """Validate an init array for n pairs -> (contiguous array, kind). A
+        "fullres" init has the engine's flow dtype, a "coarse" one is float32
+        (ValueError otherwise: a silent conversion would hide a format mix-up)."""
         if init_kind not in _INIT_KINDS or isinstance(init_kind, bool):
             raise DisError(DIS_ERR_INVALID_ARGUMENT, f"init_kind must be 'fullres' or 'coarse', not {init_kind!r}")
         kind = _INIT_KINDS[init_kind]
-        a = np.ascontiguousarray(init, dtype=np.float32)
+        want = self.flow_dtype if kind == INIT_FULLRES else np.dtype(np.float32)
+        if self.flow_dtype != np.float32 or getattr(init, "dtype", None) == np.float16:
+            if getattr(init, "dtype", None) != want:
+                raise ValueError(f"init must be {want} for init_kind {init_kind!r} on a {self.flow_dtype} engine, "
+                                 f"not {getattr(init, 'dtype', type(init).__name__)}")
+        a = np.ascontiguousarray(init, dtype=want)
         hw = (self.height, self.width) if kind == INIT_FULLRES else self._plane_shape()
         if a.shape != (n,) + hw + (2,):
             raise DisError(DIS_ERR_INVALID_ARGUMENT,
@@ -372,7 +435,9 @@ class DenseInverseSearch:
     def flow_to_init(self, flows: np.ndarray) -> np.ndarray:
         """Full-resolution (H, W, 2) or (n, H, W, 2) flows -> their init planes
         (ih, iw, 2) / (n, ih, iw, 2) (dis_flow_to_init: the reduction alone)."""
-        f = np.ascontiguousarray(flows, dtype=np.float32)
+        if self.flow_dtype != np.float32 and getattr(flows, "dtype", None) != self.flow_dtype:
+            raise ValueError(f"flows must be {self.flow_dtype} on a {self.flow_dtype} engine")
+        f = np.ascontiguousarray(flows, dtype=self.flow_dtype)
         single = f.ndim == 3
         if single:
             f = f[None]
@@ -383,7 +448,8 @@ class DenseInverseSearch:
         return out[0] if single else out
 
     def calc(self, I0: np.ndarray, I1: np.ndarray, init=None, init_kind="fullres") -> np.ndarray:
-        """u8 H x W frames (host) -> H x W x 2 float32 flow (host). init: the
+        """u8 H x W frames (host) -> H x W x 2 flow (host) of the engine's
+        flow_dtype (float32 unless the engine was made or set otherwise). init: the
         search's start, a full-resolution (H, W, 2) flow (init_kind "fullres",
         e.g. the previous pair's result) or an init plane (ih, iw, 2) ("coarse")."""
         return self.calc_batch(I0[None], I1[None], None if init is None else np.asarray(init)[None], init_kind)[0]
@@ -396,7 +462,7 @@ class DenseInverseSearch:
         n = I0.shape[0]
         if init is not None:
             init, kind = self._check_init(init, init_kind, n)
-        flow = np.empty((n, self.height, self.width, 2), np.float32)
+        flow = np.empty((n, self.height, self.width, 2), self.flow_dtype)
         if init is None:
             _check(lib().dis_calc_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
                                            self.width * self.height, _ptr(flow), MEM_HOST, None))
@@ -450,14 +516,18 @@ class DenseInverseSearch:
         if I0.shape != I1.shape or I0.ndim != 3 or I0.shape[1:] != (self.height, self.width):
             raise DisError(DIS_ERR_INVALID_ARGUMENT, f"frames must be (n, {self.height}, {self.width})")
         n = I0.shape[0]
-        fw = np.empty((n, self.height, self.width, 2), np.float32)
-        bw = np.empty((n, self.height, self.width, 2), np.float32)
+        fw = np.empty((n, self.height, self.width, 2), self.flow_dtype)
+        bw = np.empty((n, self.height, self.width, 2), self.flow_dtype)
         _check(lib().dis_calc_bidir_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
                                              self.width * self.height, _ptr(fw), _ptr(bw), MEM_HOST, None))
         if not consistency:
             return fw, bw
-        return (fw, bw, flow_consistency(fw, bw, alpha1, alpha2, device=self.device),
-                flow_consistency(bw, fw, alpha1, alpha2, device=self.device))
+        # (the check is f32-only: a float16 engine's masks come from the returned flows widened)
+        wfw, wbw = fw, bw
+        if self.flow_dtype != np.float32:
+            wfw, wbw = flow_convert(fw, np.float32, self.device), flow_convert(bw, np.float32, self.device)
+        return (fw, bw, flow_consistency(wfw, wbw, alpha1, alpha2, device=self.device),
+                flow_consistency(wbw, wfw, alpha1, alpha2, device=self.device))
 
     def calc_bidir_device(self, n: int, I0_ptr: int, I1_ptr: int, fw_ptr: int, bw_ptr: int, stream: int = 0,
                           stride: int = 0, pair_stride: int = 0) -> None:
