@@ -8,6 +8,8 @@
 //   dis::FlowFormat, dis::half_bits, dis::flowConvert
 //                             f16 flow output (set_flow_format) and the
 //                             conversion between the two formats
+//   dis::Border, dis::flowWarp
+//                             u8 images warped back by a flow field (f32 or f16)
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -45,6 +47,9 @@ enum class InitKind { COARSE = DIS_INIT_COARSE, FULLRES = DIS_INIT_FULLRES };
 // (dis_flow_format); an F16 flow is an array of IEEE binary16 bit patterns
 enum class FlowFormat { F32 = DIS_FLOW_F32, F16 = DIS_FLOW_F16 };
 using half_bits = uint16_t;
+
+// what flowWarp does with a target outside the frame (dis_border)
+enum class Border { REPLICATE = DIS_BORDER_REPLICATE, ZERO = DIS_BORDER_ZERO };
 
 class Error : public std::runtime_error {
 public:
@@ -261,6 +266,29 @@ inline void flowConvert(const void* src, FlowFormat src_format, void* dst, FlowF
 {
     check(dis_flow_convert(src, static_cast<int>(src_format), dst, static_cast<int>(dst_format), count, where, stream,
                            device));
+}
+
+// Backward warp (dis_flow_warp_u8) of n W x H u8 images of `channels` (1, 3, 4)
+// interleaved samples by n (u,v) fields, on the GPU: dst(x, y) = src sampled
+// bilinearly at (x + scale*u, y + scale*v), rounded to nearest even. With the
+// I0 -> I1 flow and src = I1, dst reconstructs I0. valid (optional): 255 where
+// the target lies inside the frame. The half_bits overload reads an F16 flow
+// as it is (no flowConvert pass).
+inline void flowWarp(const uint8_t* src, int channels, const float* flow, int n, int width, int height, uint8_t* dst,
+                     float scale = 1.0f, Border border = Border::REPLICATE, uint8_t* valid = nullptr,
+                     size_t src_stride = 0, size_t src_image_stride = 0, dis_mem where = DIS_MEM_HOST,
+                     void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_warp_u8(src, src_stride, src_image_stride, channels, flow, DIS_FLOW_F32, n, width, height, scale,
+                           static_cast<int>(border), dst, valid, where, stream, device));
+}
+inline void flowWarp(const uint8_t* src, int channels, const half_bits* flow, int n, int width, int height,
+                     uint8_t* dst, float scale = 1.0f, Border border = Border::REPLICATE, uint8_t* valid = nullptr,
+                     size_t src_stride = 0, size_t src_image_stride = 0, dis_mem where = DIS_MEM_HOST,
+                     void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_warp_u8(src, src_stride, src_image_stride, channels, flow, DIS_FLOW_F16, n, width, height, scale,
+                           static_cast<int>(border), dst, valid, where, stream, device));
 }
 
 // Middlebury .flo files (src/IO_flow.cpp ReadFlowFile / SaveFlowFile).

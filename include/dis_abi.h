@@ -130,6 +130,7 @@ dis_status dis_destroy(dis_ctx* ctx);
  * init planes, dis_flow_to_init's output, the debug dumps (DIS_STAGE_*) and
  * dis_flow_from_pyramids stay f32. dis_flow_color and dis_flow_consistency
  * take f32 fields only: dis_flow_convert is how f16 flows reach them.
+ * dis_flow_warp_u8 reads f16 flows directly (its flow_format argument).
  * Alignment of DIS_MEM_DEVICE flow pointers in DIS_FLOW_F16: 4 bytes (one
  * (u,v) pair), else DIS_ERR_INVALID_ARGUMENT; a pointer that is 8-byte aligned
  * (and an even W) gets 8-byte stores of two pixels, any other one 4-byte store
@@ -392,6 +393,47 @@ dis_status dis_flow_color(const float* flow, int n, int width, int height, float
 dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int width, int height,
                                 float alpha1, float alpha2, uint8_t* mask, float* err /* may be NULL */,
                                 dis_mem where, void* stream, int device);
+
+/* Backward warp of u8 images by flow fields (added within ABI v8, additive; no
+ * context, like dis_flow_color; no reference counterpart). With `flow` the
+ * I0 -> I1 field and `src` = I1, `dst` reconstructs I0.
+ *   src:   n images of W x H pixels of `channels` (1, 3 or 4) interleaved u8
+ *          samples; row stride src_stride bytes (0 = W*channels, else >= that),
+ *          image stride src_image_stride bytes (0 = stride*H, else >= that), as
+ *          dis_calc_batch_u8's stride / pair_stride;
+ *   flow:  n W x H (u,v) fields in the layout the engine writes, floats
+ *          (DIS_FLOW_F32) or halves (DIS_FLOW_F16, widened exactly);
+ *   dst:   n dense W x H x channels images; valid (may be NULL): n W x H bytes.
+ * For pixel (x, y) of image k with flow vector (u, v):
+ *   1. u or v NaN or |c| >= 1e9 (dis_flow_color's invalid vector, +-inf
+ *      included): every channel of dst is 0 and valid is 0, in both border modes;
+ *   2. else px = (float)x + scale*u, py = (float)y + scale*v, the product and the
+ *      sum separately rounded (scale = 1 gives exactly x + u);
+ *   3. inside = px >= 0 && px <= W-1 && py >= 0 && py <= H-1; valid = inside ? 255 : 0;
+ *   4. not inside: DIS_BORDER_ZERO writes 0 to every channel; DIS_BORDER_REPLICATE
+ *      clamps px into [0, W-1] and py into [0, H-1] and goes on;
+ *   5. x0 = floorf(px), a = px - x0, ix0 = (int)x0, ix1 = min(ix0+1, W-1), likewise
+ *      y0, b, iy0, iy1; ia = 1-a, ib = 1-b; w00 = ia*ib, w01 = a*ib, w10 = ia*b,
+ *      w11 = a*b; per channel, with p the tap's byte as a float,
+ *      s = ((w00*p00 + w01*p01) + w10*p10) + w11*p11 (dis_flow_consistency's
+ *      sampler: same taps, same order), and the output byte is rintf(s) (ties to
+ *      even) clamped to [0, 255].
+ * Every operation is a separately rounded f32 one. Every tap index comes after
+ * the invalid test and the clamp, so no input value leads to a read outside the
+ * frame. Refused with DIS_ERR_INVALID_ARGUMENT, before any device call: a null
+ * src, flow or dst; n, width or height < 1; width or height > 2^24; other
+ * channels, flow_format, border or where; strides smaller than the row / image;
+ * a scale that is not finite or has |scale| > 1024; any overlap of dst or valid
+ * with src, flow or each other; more work than one launch's grid holds; for
+ * DIS_MEM_DEVICE a flow pointer not aligned to one (u,v) pair (8 bytes F32,
+ * 4 bytes F16). Image pointers need no alignment (aligned ones and W % 4 == 0
+ * get wider accesses, same bytes). Host pointers: synchronous, staged through
+ * HIP device `device`; device pointers: asynchronous on `stream`. */
+typedef enum dis_border { DIS_BORDER_REPLICATE = 0, DIS_BORDER_ZERO = 1 } dis_border;
+dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                            const void* flow, int flow_format, int n, int width, int height,
+                            float scale, int border, uint8_t* dst, uint8_t* valid /* may be NULL */,
+                            dis_mem where, void* stream, int device);
 
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,

@@ -18,7 +18,12 @@
 // check's constants, default 0.01 0.5), --warm-start (temporal warm start: each
 // pair's search starts from the previous pair's flow, the first pair from zero;
 // one pair per GPU call, so it is refused together with --batch N > 1 and with
-// --bidir -- the pairs of one batch run concurrently and have no previous flow).
+// --bidir -- the pairs of one batch run concurrently and have no previous flow),
+// --warp (also write OF_<folder>/frame_NNNN_warp.png: the pair's second frame
+// warped back by the computed -- with --bidir, the forward -- flow, 8-bit grey,
+// targets outside the frame clamped; and print the mean absolute difference to
+// the first frame over the pixels whose target lies inside the frame, next to
+// the unwarped second frame's).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -55,7 +60,7 @@ void usage()
                  "3. Add full settings\n"
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
-                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start"
+                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp"
               << std::endl;
 }
 
@@ -77,7 +82,7 @@ int main(int argc, char** argv)
     int draw_grid = 0;
     bool write_flo = false;
     int batch = 8, device = 0;
-    bool bidir = false, warm_start = false, batch_given = false;
+    bool bidir = false, warm_start = false, batch_given = false, warp = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
 
     std::vector<std::string> pos;
@@ -94,6 +99,8 @@ int main(int argc, char** argv)
             bidir = true;
         } else if (a == "--warm-start") {
             warm_start = true;
+        } else if (a == "--warp") {
+            warp = true;
         } else if (a == "--fb-alpha" && i + 2 < argc) {
             fb_alpha1 = (float)std::atof(argv[++i]);
             fb_alpha2 = (float)std::atof(argv[++i]);
@@ -186,9 +193,30 @@ int main(int argc, char** argv)
             }
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
+            std::vector<uint8_t> warped, inside;
+            if (warp) {
+                warped.resize((size_t)n * W * H);
+                inside.resize((size_t)n * W * H);
+                dis::flowWarp(I1.data(), 1, flow.data(), n, W, H, warped.data(), 1.0f, dis::Border::REPLICATE,
+                              inside.data(), 0, 0, DIS_MEM_HOST, nullptr, device);
+            }
             for (int k = 0; k < n; ++k) {
                 const std::string base = "OF_" + frame_name(folder, i0 + k);
                 png::write_bgr(base + ".png", bgr.data() + (size_t)k * W * H * 3, W, H);
+                if (warp) {
+                    const size_t o = (size_t)k * W * H;
+                    png::write_gray(base + "_warp.png", warped.data() + o, W, H);
+                    long long cnt = 0, d_warp = 0, d_plain = 0;
+                    for (size_t q = o; q < o + (size_t)W * H; ++q)
+                        if (inside[q]) {
+                            ++cnt;
+                            d_warp += std::abs((int)warped[q] - (int)I0[q]);
+                            d_plain += std::abs((int)I1[q] - (int)I0[q]);
+                        }
+                    std::cout << "warp " << frame_name(folder, i0 + k) << ".png: mean |warped - first| "
+                              << (cnt ? (double)d_warp / cnt : 0.0) << ", mean |second - first| "
+                              << (cnt ? (double)d_plain / cnt : 0.0) << " over " << cnt << " valid pixels" << std::endl;
+                }
                 if (write_flo)
                     dis::check(dis_write_flo((base + ".flo").c_str(), flow.data() + (size_t)k * W * H * 2, W, H, 2));
                 if (bidir) {

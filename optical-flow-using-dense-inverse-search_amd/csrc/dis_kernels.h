@@ -179,6 +179,16 @@ long long flow_consistency_blocks(int n, int W, int H);  // grid size of the lau
 hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int W, int H, float alpha1,
                                    float alpha2, uint8_t* mask, float* err, hipStream_t s, Timing t = {});
 
+// Backward warp of n W x H u8 images of `channels` (1, 3, 4) interleaved
+// samples by n (u,v) fields (dis_warp.hip): dst(x, y) = src sampled bilinearly
+// at (x + scale * u, y + scale * v); valid (u8, 255 = target inside the frame)
+// may be null. f16 != 0: `flow` holds __half2 vectors (4-byte aligned), else
+// float2 (8-byte aligned). Strides in bytes, already resolved (never 0).
+long long flow_warp_blocks(int n, int W, int H);  // grid size of the launch
+hipError_t launch_flow_warp(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                            const void* flow, int f16, int n, int W, int H, float scale, int zero_border,
+                            uint8_t* dst, uint8_t* valid, hipStream_t s, Timing t = {});
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

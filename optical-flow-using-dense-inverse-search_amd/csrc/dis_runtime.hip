@@ -2201,4 +2201,85 @@ dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int wid
     return rc;
 }
 
+dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                            const void* flow, int flow_format, int n, int width, int height, float scale, int border,
+                            uint8_t* dst, uint8_t* valid, dis_mem where, void* stream, int device)
+{
+    if (!src || !flow || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
+    // pixel coordinates are exact floats
+    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
+    if (flow_format != DIS_FLOW_F32 && flow_format != DIS_FLOW_F16)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (border != DIS_BORDER_REPLICATE && border != DIS_BORDER_ZERO)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "border must be DIS_BORDER_REPLICATE or DIS_BORDER_ZERO");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!std::isfinite(scale) || std::fabs(scale) > 1024.0f)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "scale must be finite with |scale| <= 1024");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    // (it also keeps every byte count below far under 2^63)
+    if (dis::flow_warp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    const size_t row = (size_t)width * channels;
+    const size_t stride = src_stride ? src_stride : row;
+    if (stride < row) return fail(DIS_ERR_INVALID_ARGUMENT, "src_stride smaller than a row");
+    if (stride > (size_t(1) << 48) / (size_t)height) return fail(DIS_ERR_INVALID_ARGUMENT, "src_stride too large");
+    const size_t image_stride = src_image_stride ? src_image_stride : stride * height;
+    if (image_stride < stride * height) return fail(DIS_ERR_INVALID_ARGUMENT, "src_image_stride smaller than an image");
+    if (image_stride > (size_t(1) << 62) / (size_t)n) return fail(DIS_ERR_INVALID_ARGUMENT, "src_image_stride too large");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    struct Range {
+        uintptr_t p;
+        size_t bytes;
+        const char* name;
+    };
+    const Range in[2] = {{reinterpret_cast<uintptr_t>(src), (n - 1) * image_stride + (height - 1) * stride + row, "src"},
+                         {reinterpret_cast<uintptr_t>(flow), px * fsz, "flow"}};
+    const Range out[2] = {{reinterpret_cast<uintptr_t>(dst), px * channels, "dst"},
+                          {reinterpret_cast<uintptr_t>(valid), px, "valid"}};
+    const auto overlap = [](const Range& a, const Range& b) { return a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
+    for (int o = 0; o < (valid ? 2 : 1); ++o)
+        for (int i = 0; i < 2; ++i)
+            if (overlap(out[o], in[i]))
+                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + in[i].name + " overlap");
+    if (valid && overlap(out[0], out[1])) return fail(DIS_ERR_INVALID_ARGUMENT, "dst and valid overlap");
+    if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(flow) & (fsz - 1)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    DIS_HIP(hipSetDevice(device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int f16 = flow_format == DIS_FLOW_F16, zero = border == DIS_BORDER_ZERO;
+    if (where == DIS_MEM_DEVICE) {
+        DIS_HIP(dis::launch_flow_warp(src, stride, image_stride, channels, flow, f16, n, width, height, scale, zero, dst,
+                                      valid, s));
+        return DIS_OK;
+    }
+    // the source is staged as it lies (rows and images keep their strides)
+    uint8_t *dsrc = nullptr, *ddst = nullptr, *dvalid = nullptr;
+    void* dflow = nullptr;
+    dis_status rc = DIS_OK;
+    if (hipMalloc(&dsrc, in[0].bytes) != hipSuccess || hipMalloc(&dflow, in[1].bytes) != hipSuccess ||
+        hipMalloc(&ddst, out[0].bytes) != hipSuccess || (valid && hipMalloc(&dvalid, px) != hipSuccess)) {
+        (void)hipGetLastError();
+        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
+    } else if (hipMemcpyAsync(dsrc, src, in[0].bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipMemcpyAsync(dflow, flow, in[1].bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+               dis::launch_flow_warp(dsrc, stride, image_stride, channels, dflow, f16, n, width, height, scale, zero,
+                                     ddst, dvalid, s) != hipSuccess ||
+               hipMemcpyAsync(dst, ddst, out[0].bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               (valid && hipMemcpyAsync(valid, dvalid, px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+               hipStreamSynchronize(s) != hipSuccess) {
+        rc = fail(DIS_ERR_DEVICE, "flow warp failed");
+    }
+    hipFree(dsrc);
+    hipFree(dflow);
+    hipFree(ddst);
+    hipFree(dvalid);
+    return rc;
+}
+
 }  // extern "C"

@@ -55,6 +55,8 @@ INIT_COARSE, INIT_FULLRES = 0, 1
 
 FLOW_F32, FLOW_F16 = 0, 1  # dis_flow_format
 
+BORDER_REPLICATE, BORDER_ZERO = 0, 1  # dis_border
+
 
 def _flow_format(dtype) -> int:
     """dis_flow_format of a flow dtype (np.float32 / np.float16); ValueError for any other."""
@@ -70,6 +72,8 @@ def _flow_format(dtype) -> int:
 
 
 _FLOW_DTYPES = {FLOW_F32: np.dtype(np.float32), FLOW_F16: np.dtype(np.float16)}
+_BORDERS = {"replicate": BORDER_REPLICATE, "zero": BORDER_ZERO, BORDER_REPLICATE: BORDER_REPLICATE,
+            BORDER_ZERO: BORDER_ZERO}
 _INIT_KINDS = {"coarse": INIT_COARSE, "fullres": INIT_FULLRES, INIT_COARSE: INIT_COARSE, INIT_FULLRES: INIT_FULLRES}
 
 # Every symbol include/dis_abi.h declares (checked by tests/test_abi.py).
@@ -83,7 +87,7 @@ EXPORTED_SYMBOLS = (
     "dis_host_alloc", "dis_host_free", "dis_batch_stream_plan", "dis_check_stream_plan",
     "dis_calc_bidir_batch_u8", "dis_flow_consistency",
     "dis_init_plane_size", "dis_flow_to_init", "dis_calc_batch_init_u8",
-    "dis_set_flow_format", "dis_flow_convert",
+    "dis_set_flow_format", "dis_flow_convert", "dis_flow_warp_u8",
 )
 
 
@@ -203,6 +207,8 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_set_flow_format"):  # (added within v8)
             L.dis_set_flow_format.argtypes = [V, I]
             L.dis_flow_convert.argtypes = [V, I, V, I, Z, I, V, I]
+        if hasattr(L, "dis_flow_warp_u8"):  # (added within v8)
+            L.dis_flow_warp_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, F, I, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -314,6 +320,66 @@ def flow_convert_device(src_ptr: int, src_dtype, dst_ptr: int, dst_dtype, count:
     """dis_flow_convert on raw device pointers (`count` values), asynchronous on `stream`."""
     _check(lib().dis_flow_convert(src_ptr, _flow_format(src_dtype), dst_ptr, _flow_format(dst_dtype), count,
                                   MEM_DEVICE, stream or None, device))
+
+
+def _border(border) -> int:
+    try:
+        return _BORDERS[border]
+    except (KeyError, TypeError):
+        raise ValueError(f"border must be 'replicate' or 'zero', not {border!r}") from None
+
+
+def flow_warp(image: np.ndarray, flow: np.ndarray, scale: float = 1.0, border="replicate",
+              with_valid: bool = False, device: int = 0):
+    """Backward warp (dis_flow_warp_u8) of u8 images by flow fields on the GPU:
+    out(x, y) = image sampled bilinearly at (x + scale*u, y + scale*v), rounded
+    to nearest even; with the I0 -> I1 flow and image = I1 the result
+    reconstructs I0. image: (H, W), (H, W, C), (n, H, W) or (n, H, W, C) with C
+    in 1, 3, 4 (a 3-D image is (H, W, C) when its leading dimensions match the
+    flow's (H, W), else (n, H, W)); flow: float32 or float16 (..., H, W, 2),
+    read in its own dtype. border: "replicate" (targets outside the frame are
+    clamped) or "zero". Returns the warped array of the image's shape; with_valid:
+    also the u8 mask (..., H, W), 255 where the target lies inside the frame.
+    Invalid vectors (NaN, |c| >= 1e9) give 0 and valid 0."""
+    fl = np.asarray(flow)
+    fmt = _flow_format(fl.dtype)
+    bd = _border(border)
+    img = np.asarray(image)
+    if img.dtype != np.uint8:
+        raise ValueError(f"image dtype must be uint8, not {img.dtype}")
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError("flow must be (H, W, 2) or (n, H, W, 2)")
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    if img.ndim == 2:
+        shape4 = (1,) + img.shape + (1,)
+    elif img.ndim == 3:
+        shape4 = (1,) + img.shape if img.shape[:2] == (H, W) else img.shape + (1,)
+    elif img.ndim == 4:
+        shape4 = img.shape
+    else:
+        raise ValueError("image must be (H, W), (H, W, C), (n, H, W) or (n, H, W, C)")
+    if shape4[:3] != (n, H, W):
+        raise ValueError(f"image shape {img.shape} does not match flow shape {fl.shape}")
+    C = shape4[3]
+    if C not in (1, 3, 4):
+        raise ValueError(f"image must have 1, 3 or 4 channels, not {C}")
+    img = np.ascontiguousarray(img)
+    fl = np.ascontiguousarray(fl)
+    out = np.empty(img.shape, np.uint8)
+    valid = np.empty(fl.shape[:-1], np.uint8) if with_valid else None
+    _check(lib().dis_flow_warp_u8(_ptr(img), 0, 0, C, _ptr(fl), fmt, n, W, H, float(scale), bd, _ptr(out),
+                                  _ptr(valid) if with_valid else None, MEM_HOST, None, device))
+    return (out, valid) if with_valid else out
+
+
+def flow_warp_device(src_ptr: int, flow_ptr: int, flow_dtype, n: int, width: int, height: int, channels: int,
+                     dst_ptr: int, valid_ptr: int = 0, scale: float = 1.0, border="replicate", src_stride: int = 0,
+                     src_image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_flow_warp_u8 on raw device pointers, asynchronous on `stream`."""
+    fmt, bd = _flow_format(flow_dtype), _border(border)
+    _check(lib().dis_flow_warp_u8(src_ptr, src_stride, src_image_stride, channels, flow_ptr, fmt, n, width, height,
+                                  float(scale), bd, dst_ptr, valid_ptr or None, MEM_DEVICE, stream or None, device))
 
 
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
