@@ -10,6 +10,8 @@
 //                             conversion between the two formats
 //   dis::Border, dis::flowWarp
 //                             u8 images warped back by a flow field (f32 or f16)
+//   dis::flowInterp, dis::flowInterpWorkspace
+//                             the frame at time t between two u8 images
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -289,6 +291,37 @@ inline void flowWarp(const uint8_t* src, int channels, const half_bits* flow, in
 {
     check(dis_flow_warp_u8(src, src_stride, src_image_stride, channels, flow, DIS_FLOW_F16, n, width, height, scale,
                            static_cast<int>(border), dst, valid, where, stream, device));
+}
+
+// The frame at time t in [0, 1] between n pairs of W x H u8 images
+// (dis_flow_interp_u8), on the GPU: the forward flow fw (I0 -> I1) projected to
+// time t, collisions resolved by photoconsistency, both frames sampled with
+// the projected flow; holes filled from I1 through bw (I1 -> I0, may be null)
+// or with fw's own vector. fill (optional): 0 = a projected vector, 1 = from
+// bw, 2 = from fw. Device pointers need a workspace of flowInterpWorkspace(n,
+// width, height) bytes, 8-byte aligned; host pointers need none. The half_bits
+// overload reads F16 flows as they are.
+inline size_t flowInterpWorkspace(int n, int width, int height)
+{
+    size_t bytes = 0;
+    check(dis_flow_interp_workspace(n, width, height, &bytes));
+    return bytes;
+}
+inline void flowInterp(const uint8_t* I0, const uint8_t* I1, int channels, const float* fw, const float* bw, int n,
+                       int width, int height, float t, uint8_t* dst, uint8_t* fill = nullptr,
+                       void* workspace = nullptr, size_t stride = 0, size_t image_stride = 0,
+                       dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_interp_u8(I0, I1, stride, image_stride, channels, fw, bw, DIS_FLOW_F32, n, width, height, t, dst,
+                             fill, workspace, where, stream, device));
+}
+inline void flowInterp(const uint8_t* I0, const uint8_t* I1, int channels, const half_bits* fw, const half_bits* bw,
+                       int n, int width, int height, float t, uint8_t* dst, uint8_t* fill = nullptr,
+                       void* workspace = nullptr, size_t stride = 0, size_t image_stride = 0,
+                       dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_interp_u8(I0, I1, stride, image_stride, channels, fw, bw, DIS_FLOW_F16, n, width, height, t, dst,
+                             fill, workspace, where, stream, device));
 }
 
 // Middlebury .flo files (src/IO_flow.cpp ReadFlowFile / SaveFlowFile).

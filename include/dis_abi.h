@@ -435,6 +435,65 @@ dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_im
                             float scale, int border, uint8_t* dst, uint8_t* valid /* may be NULL */,
                             dis_mem where, void* stream, int device);
 
+/* The frame at time t in [0, 1] between I0 (t = 0) and I1 (t = 1) (added within
+ * ABI v8, additive; no context, like dis_flow_warp_u8; no reference counterpart):
+ * the Middlebury interpolation algorithm (Baker et al., IJCV 2011, section 3.3).
+ * The forward flow is projected to time t, collisions go to the photoconsistent
+ * candidate, holes are filled apart, and both frames are sampled with the
+ * projected flow.
+ *   I0, I1: n images each of W x H pixels of `channels` (1, 3 or 4) interleaved
+ *           u8 samples; both with row stride `stride` and image stride
+ *           `image_stride` in bytes (0 = dense), dis_flow_warp_u8's conventions;
+ *   fw, bw: the I0 -> I1 and the I1 -> I0 fields, n W x H (u,v) each, both floats
+ *           (DIS_FLOW_F32) or both halves (DIS_FLOW_F16, widened exactly); bw may
+ *           be NULL;
+ *   dst:    n dense W x H x channels images; fill (may be NULL): n W x H bytes;
+ *   workspace: n*W*H uint64 keys (dis_flow_interp_workspace gives the bytes),
+ *           8-byte aligned; required for DIS_MEM_DEVICE, ignored for DIS_MEM_HOST
+ *           (the call stages everything and allocates its own).
+ * Every f32 operation is separately rounded. tb = 1.0f - t. A vector (u, v) is
+ * valid when |u| < 1e9 && |v| < 1e9 (false for NaN). sample(I, x, y, u, v, k)
+ * is dis_flow_warp_u8's steps 2-5 with scale k and DIS_BORDER_REPLICATE on
+ * image I at pixel (x, y): px = (float)x + k*u, py = (float)y + k*v, the `inside`
+ * flag, the clamp, and the unrounded sum s of every channel.
+ *   1. Splat. Pixel (x, y) of I0 takes part when fw(x, y) = (u, v) is valid and
+ *      sample(I1, x, y, u, v, 1) is inside. cost = sum over the channels, in
+ *      their order, of |(float)I0_c(x, y) - s_c|; key = (uint64)bits(cost) << 32 |
+ *      (y*W + x). tx = (float)x + t*u, ty = (float)y + t*v; the targets are
+ *      {floorf(tx), ceilf(tx)} x {floorf(ty), ceilf(ty)} without duplicates
+ *      and without those outside [0, W-1] x [0, H-1] (tested as floats); each
+ *      target q gets workspace[k*W*H + q] = min(itself, key), from ~0 at the start.
+ *      The bits of a non-negative float order as unsigned integers, so the lowest
+ *      cost wins and, among equal costs, the lowest source index: a minimum over
+ *      distinct keys does not depend on the order of arrival, and every run
+ *      writes the same bytes.
+ *   2. Blend. For output pixel (x, y) with key K:
+ *      K != ~0: (u, v) = fw at source index K & 0xffffffff, fill = 0;
+ *        s0 = sample(I0, x, y, u, v, -t), s1 = sample(I1, x, y, u, v, tb);
+ *        both inside or neither: r = tb*s0 + t*s1 (two products, one sum);
+ *        only s0 inside: r = s0; only s1 inside: r = s1;
+ *      K == ~0, bw given, bw(x, y) valid and sample(I1, x, y, bw, -tb) inside:
+ *        r = that sample, fill = 1 (a disoccluded pixel, visible only in I1);
+ *      any other hole: fill = 2, (u, v) = fw(x, y), or (0, 0) if that is not
+ *        valid, and the three cases of K != ~0.
+ *      The output byte is rintf(r) (ties to even) clamped to [0, 255].
+ * No tap or target index is formed before the validity test and the clamp or
+ * the frame test. t = 1 gives I1 exactly; t = 0 gives I0 exactly when bw is NULL.
+ * Refused with DIS_ERR_INVALID_ARGUMENT, before any device call:
+ * dis_flow_warp_u8's list (null I0, I1, fw or dst; sizes; channels; flow_format;
+ * where; strides; the grid), a t that is not finite or lies outside [0, 1],
+ * W*H > 2^31, any overlap of dst, fill or workspace with I0, I1, fw, bw or each
+ * other, and for DIS_MEM_DEVICE a NULL workspace, one that is not 8-byte aligned,
+ * or an fw or bw not aligned to one (u,v) pair. Host pointers: synchronous,
+ * staged through HIP device `device`; device pointers: asynchronous on `stream`
+ * (one hipMemsetAsync of the workspace to 0xFF, then two kernel launches). */
+dis_status dis_flow_interp_workspace(int n, int width, int height, size_t* bytes); /* n*W*H*8 */
+dis_status dis_flow_interp_u8(const uint8_t* I0, const uint8_t* I1, size_t stride, size_t image_stride,
+                              int channels, const void* fw, const void* bw /* may be NULL */, int flow_format,
+                              int n, int width, int height, float t,
+                              uint8_t* dst, uint8_t* fill /* may be NULL */,
+                              void* workspace, dis_mem where, void* stream, int device);
+
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,
  * little-endian; channels 1 (depth), 2 (flow) or 4 (scene flow). Host only

@@ -23,7 +23,11 @@
 // warped back by the computed -- with --bidir, the forward -- flow, 8-bit grey,
 // targets outside the frame clamped; and print the mean absolute difference to
 // the first frame over the pixels whose target lies inside the frame, next to
-// the unwarped second frame's).
+// the unwarped second frame's), --interp K (also write
+// OF_<folder>/frame_NNNN_interp_k.png for k = 1..K: the frame at time
+// t = k / (K + 1) between the pair's two frames, 8-bit grey, interpolated with
+// the computed flow by dis::flowInterp; holes are filled from the backward flow
+// with --bidir, from the forward flow alone without).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -60,7 +64,8 @@ void usage()
                  "3. Add full settings\n"
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
-                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp"
+                 "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
+                 "--interp K"
               << std::endl;
 }
 
@@ -84,6 +89,7 @@ int main(int argc, char** argv)
     int batch = 8, device = 0;
     bool bidir = false, warm_start = false, batch_given = false, warp = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
+    int interp = 0;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -101,6 +107,8 @@ int main(int argc, char** argv)
             warm_start = true;
         } else if (a == "--warp") {
             warp = true;
+        } else if (a == "--interp" && i + 1 < argc) {
+            interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
             fb_alpha1 = (float)std::atof(argv[++i]);
             fb_alpha2 = (float)std::atof(argv[++i]);
@@ -134,6 +142,10 @@ int main(int argc, char** argv)
         return 2;
     }
     if (batch < 1) batch = 1;
+    if (interp < 0 || interp > 99) {
+        std::cerr << "--interp K: K must lie in [0, 99]" << std::endl;
+        return 2;
+    }
     if (warm_start && ((batch_given && batch > 1) || bidir)) {
         std::cerr << "--warm-start seeds each pair from the previous pair's flow: it cannot be combined with "
                   << (bidir ? "--bidir" : "--batch N > 1")
@@ -199,6 +211,15 @@ int main(int argc, char** argv)
                 inside.resize((size_t)n * W * H);
                 dis::flowWarp(I1.data(), 1, flow.data(), n, W, H, warped.data(), 1.0f, dis::Border::REPLICATE,
                               inside.data(), 0, 0, DIS_MEM_HOST, nullptr, device);
+            }
+            std::vector<uint8_t> mid((size_t)n * W * H);
+            for (int j = 1; j <= interp; ++j) {
+                dis::flowInterp(I0.data(), I1.data(), 1, flow.data(), bidir ? flow_bw.data() : nullptr, n, W, H,
+                                (float)j / (float)(interp + 1), mid.data(), nullptr, nullptr, 0, 0, DIS_MEM_HOST,
+                                nullptr, device);
+                for (int k = 0; k < n; ++k)
+                    png::write_gray("OF_" + frame_name(folder, i0 + k) + "_interp_" + std::to_string(j) + ".png",
+                                    mid.data() + (size_t)k * W * H, W, H);
             }
             for (int k = 0; k < n; ++k) {
                 const std::string base = "OF_" + frame_name(folder, i0 + k);

@@ -189,6 +189,20 @@ hipError_t launch_flow_warp(const uint8_t* src, size_t src_stride, size_t src_im
                             const void* flow, int f16, int n, int W, int H, float scale, int zero_border,
                             uint8_t* dst, uint8_t* valid, hipStream_t s, Timing t = {});
 
+// The frame at time t in [0, 1] between n pairs of W x H u8 images (dis_interp.hip,
+// dis_flow_interp_u8): one memset of `workspace` (n * W * H 64-bit keys, 8-byte
+// aligned) to 0xFF, k_interp_splat (the forward flow projected to time t by
+// atomicMin on the keys) and k_interp_blend (both frames sampled with the
+// winning vectors; holes from bw, which may be null, or fw). I0 and I1 share
+// the strides (bytes, already resolved); fw and bw as launch_flow_warp's flow;
+// fill (u8, 0 / 1 / 2) may be null. flow_interp_blocks(n, W, H) >= 1: the
+// splat's grid (a lane per pixel), -1 when W * H > 2^31 or the grid limit is
+// exceeded.
+long long flow_interp_blocks(int n, int W, int H);
+hipError_t launch_flow_interp(const uint8_t* I0, const uint8_t* I1, size_t stride, size_t image_stride, int channels,
+                              const void* fw, const void* bw, int f16, int n, int W, int H, float t, uint8_t* dst,
+                              uint8_t* fill, void* workspace, hipStream_t s, Timing t_splat = {}, Timing t_blend = {});
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

@@ -2282,4 +2282,117 @@ dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_im
     return rc;
 }
 
+dis_status dis_flow_interp_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
+    if (width > (1 << 24) || height > (1 << 24) || (long long)width * height > (1ll << 31))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
+    if (dis::flow_interp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    *bytes = sizeof(uint64_t) * (size_t)width * height * n;
+    return DIS_OK;
+}
+
+dis_status dis_flow_interp_u8(const uint8_t* I0, const uint8_t* I1, size_t stride_in, size_t image_stride_in, int channels,
+                              const void* fw, const void* bw, int flow_format, int n, int width, int height, float t,
+                              uint8_t* dst, uint8_t* fill, void* workspace, dis_mem where, void* stream, int device)
+{
+    if (!I0 || !I1 || !fw || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
+    // pixel coordinates are exact floats
+    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
+    // a source index fills the low half of a key
+    if ((long long)width * height > (1ll << 31)) return fail(DIS_ERR_INVALID_ARGUMENT, "width * height must be <= 2^31");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
+    if (flow_format != DIS_FLOW_F32 && flow_format != DIS_FLOW_F16)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!(t >= 0.0f && t <= 1.0f)) return fail(DIS_ERR_INVALID_ARGUMENT, "t must lie in [0, 1]");  // also NaN
+    // the splat folds n * W * H pixels into a one-dimensional grid: its size is the only limit on n
+    // (it also keeps every byte count below far under 2^63)
+    if (dis::flow_interp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    const size_t row = (size_t)width * channels;
+    const size_t stride = stride_in ? stride_in : row;
+    if (stride < row) return fail(DIS_ERR_INVALID_ARGUMENT, "stride smaller than a row");
+    if (stride > (size_t(1) << 48) / (size_t)height) return fail(DIS_ERR_INVALID_ARGUMENT, "stride too large");
+    const size_t image_stride = image_stride_in ? image_stride_in : stride * height;
+    if (image_stride < stride * height) return fail(DIS_ERR_INVALID_ARGUMENT, "image_stride smaller than an image");
+    if (image_stride > (size_t(1) << 62) / (size_t)n) return fail(DIS_ERR_INVALID_ARGUMENT, "image_stride too large");
+    const bool dev = where == DIS_MEM_DEVICE;
+    if (dev && !workspace) return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers need a workspace");
+    if (dev && (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "workspace must be 8-byte aligned");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    const size_t ibytes = (n - 1) * image_stride + (height - 1) * stride + row;
+    struct Range {
+        uintptr_t p;
+        size_t bytes;
+        const char* name;
+    };
+    // (a null bw, a null fill and a host call's workspace take no part)
+    const Range in[4] = {{reinterpret_cast<uintptr_t>(I0), ibytes, "I0"},
+                         {reinterpret_cast<uintptr_t>(I1), ibytes, "I1"},
+                         {reinterpret_cast<uintptr_t>(fw), px * fsz, "fw"},
+                         {reinterpret_cast<uintptr_t>(bw), bw ? px * fsz : 0, "bw"}};
+    const Range out[3] = {{reinterpret_cast<uintptr_t>(dst), px * channels, "dst"},
+                          {reinterpret_cast<uintptr_t>(fill), fill ? px : 0, "fill"},
+                          {reinterpret_cast<uintptr_t>(workspace), dev ? px * sizeof(uint64_t) : 0, "workspace"}};
+    const auto overlap = [](const Range& a, const Range& b) {
+        return a.bytes && b.bytes && a.p < b.p + b.bytes && b.p < a.p + a.bytes;
+    };
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 4; ++i)
+            if (overlap(out[o], in[i]))
+                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + in[i].name + " overlap");
+        for (int q = o + 1; q < 3; ++q)
+            if (overlap(out[o], out[q]))
+                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + out[q].name + " overlap");
+    }
+    if (dev && ((reinterpret_cast<uintptr_t>(fw) | reinterpret_cast<uintptr_t>(bw)) & (fsz - 1)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    DIS_HIP(hipSetDevice(device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int f16 = flow_format == DIS_FLOW_F16;
+    if (dev) {
+        DIS_HIP(dis::launch_flow_interp(I0, I1, stride, image_stride, channels, fw, bw, f16, n, width, height, t, dst,
+                                        fill, workspace, s));
+        return DIS_OK;
+    }
+    // the frames are staged as they lie (rows and images keep their strides)
+    uint8_t *d0 = nullptr, *d1 = nullptr, *ddst = nullptr, *dfill = nullptr;
+    void *dfw = nullptr, *dbw = nullptr, *dws = nullptr;
+    dis_status rc = DIS_OK;
+    if (hipMalloc(&d0, ibytes) != hipSuccess || hipMalloc(&d1, ibytes) != hipSuccess ||
+        hipMalloc(&dfw, px * fsz) != hipSuccess || (bw && hipMalloc(&dbw, px * fsz) != hipSuccess) ||
+        hipMalloc(&ddst, px * channels) != hipSuccess || (fill && hipMalloc(&dfill, px) != hipSuccess) ||
+        hipMalloc(&dws, px * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
+    } else if (hipMemcpyAsync(d0, I0, ibytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipMemcpyAsync(d1, I1, ibytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+               hipMemcpyAsync(dfw, fw, px * fsz, hipMemcpyHostToDevice, s) != hipSuccess ||
+               (bw && hipMemcpyAsync(dbw, bw, px * fsz, hipMemcpyHostToDevice, s) != hipSuccess) ||
+               dis::launch_flow_interp(d0, d1, stride, image_stride, channels, dfw, dbw, f16, n, width, height, t, ddst,
+                                       dfill, dws, s) != hipSuccess ||
+               hipMemcpyAsync(dst, ddst, px * channels, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               (fill && hipMemcpyAsync(fill, dfill, px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+               hipStreamSynchronize(s) != hipSuccess) {
+        rc = fail(DIS_ERR_DEVICE, "flow interpolation failed");
+    }
+    hipFree(d0);
+    hipFree(d1);
+    hipFree(dfw);
+    hipFree(dbw);
+    hipFree(ddst);
+    hipFree(dfill);
+    hipFree(dws);
+    return rc;
+}
+
 }  // extern "C"

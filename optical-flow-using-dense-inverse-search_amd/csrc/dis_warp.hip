@@ -15,12 +15,14 @@
 // f32, one for f16), one dword tap for 4 channels, and dword (1 and 3
 // channels) or 16-byte (4 channels) image stores plus one dword of mask, when
 // pointers and W allow (chosen at run time, as k_fb_check's forms are); the
-// scalar forms write the same bytes. No LDS, no atomics.
+// scalar forms write the same bytes. No LDS, no atomics. The per-pixel
+// sampler (warp_pixel) lives in dis_sample.h, which dis_interp.hip shares.
 #include <cmath>
 #include <cstdint>
 
 #include "dis_half.h"
 #include "dis_kernels.h"
+#include "dis_sample.h"
 
 namespace dis {
 namespace {
@@ -42,65 +44,6 @@ struct WarpArgs {
     int vec_dst;       // dst 4-byte (4 channels: 16-byte) aligned and W % 4 == 0: dword / 16-byte stores
     int vec_valid;     // valid 4-byte aligned and W % 4 == 0: one dword per lane
 };
-
-// One pixel: S = this pixel's source image, (u, v) its flow vector. Writes the
-// C output bytes to o[], returns the valid byte.
-template <int C>
-__device__ __forceinline__ unsigned warp_pixel(const uint8_t* __restrict__ S, long long stride, int x, int y, int W,
-                                               int H, float u, float v, float scale, int zero_border, int vec_tap,
-                                               unsigned* o)
-{
-#pragma unroll
-    for (int c = 0; c < C; ++c) o[c] = 0u;
-    if (!(fabsf(u) < 1e9f && fabsf(v) < 1e9f)) return 0u;  // also NaN
-    const float su = scale * u, sv = scale * v;
-    float px = (float)x + su, py = (float)y + sv;  // finite: |scale| <= 1024
-    const float xm = (float)(W - 1), ym = (float)(H - 1);
-    const bool inside = px >= 0.0f && px <= xm && py >= 0.0f && py <= ym;
-    if (!inside) {
-        if (zero_border) return 0u;
-        px = fminf(fmaxf(px, 0.0f), xm);
-        py = fminf(fmaxf(py, 0.0f), ym);
-    }
-    const float x0 = floorf(px), y0 = floorf(py);
-    const float a = px - x0, b = py - y0;
-    const int ix0 = (int)x0, iy0 = (int)y0;  // in [0, W-1] x [0, H-1]
-    const int ix1 = min(ix0 + 1, W - 1), iy1 = min(iy0 + 1, H - 1);
-    const float ia = 1.0f - a, ib = 1.0f - b;
-    const float w00 = ia * ib, w01 = a * ib, w10 = ia * b, w11 = a * b;
-    const uint8_t* const r0 = S + iy0 * stride;
-    const uint8_t* const r1 = S + iy1 * stride;
-    unsigned t00[C], t01[C], t10[C], t11[C];
-    if (C == 4 && vec_tap) {
-        const unsigned d00 = *reinterpret_cast<const unsigned*>(r0 + 4 * ix0);
-        const unsigned d01 = *reinterpret_cast<const unsigned*>(r0 + 4 * ix1);
-        const unsigned d10 = *reinterpret_cast<const unsigned*>(r1 + 4 * ix0);
-        const unsigned d11 = *reinterpret_cast<const unsigned*>(r1 + 4 * ix1);
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            t00[c] = (d00 >> (8 * c)) & 255u;
-            t01[c] = (d01 >> (8 * c)) & 255u;
-            t10[c] = (d10 >> (8 * c)) & 255u;
-            t11[c] = (d11 >> (8 * c)) & 255u;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            t00[c] = r0[C * ix0 + c];
-            t01[c] = r0[C * ix1 + c];
-            t10[c] = r1[C * ix0 + c];
-            t11[c] = r1[C * ix1 + c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float s = ((w00 * (float)t00[c] + w01 * (float)t01[c]) + w10 * (float)t10[c]) + w11 * (float)t11[c];
-        o[c] = (unsigned)fminf(fmaxf(rintf(s), 0.0f), 255.0f);
-    }
-    return inside ? 255u : 0u;
-}
-
-__device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
 
 template <int C, bool F16>
 __global__ void __launch_bounds__(kWarpThreads) k_flow_warp(WarpArgs a)

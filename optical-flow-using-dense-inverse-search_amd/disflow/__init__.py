@@ -88,6 +88,7 @@ EXPORTED_SYMBOLS = (
     "dis_calc_bidir_batch_u8", "dis_flow_consistency",
     "dis_init_plane_size", "dis_flow_to_init", "dis_calc_batch_init_u8",
     "dis_set_flow_format", "dis_flow_convert", "dis_flow_warp_u8",
+    "dis_flow_interp_workspace", "dis_flow_interp_u8",
 )
 
 
@@ -209,6 +210,9 @@ def lib() -> ctypes.CDLL:
             L.dis_flow_convert.argtypes = [V, I, V, I, Z, I, V, I]
         if hasattr(L, "dis_flow_warp_u8"):  # (added within v8)
             L.dis_flow_warp_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, F, I, V, V, I, V, I]
+        if hasattr(L, "dis_flow_interp_u8"):  # (added within v8)
+            L.dis_flow_interp_workspace.argtypes = [I, I, I, P(Z)]
+            L.dis_flow_interp_u8.argtypes = [V, V, Z, Z, I, V, V, I, I, I, I, F, V, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -380,6 +384,81 @@ def flow_warp_device(src_ptr: int, flow_ptr: int, flow_dtype, n: int, width: int
     fmt, bd = _flow_format(flow_dtype), _border(border)
     _check(lib().dis_flow_warp_u8(src_ptr, src_stride, src_image_stride, channels, flow_ptr, fmt, n, width, height,
                                   float(scale), bd, dst_ptr, valid_ptr or None, MEM_DEVICE, stream or None, device))
+
+
+def flow_interp_workspace(n: int, width: int, height: int) -> int:
+    """Bytes of dis_flow_interp_u8's workspace for n W x H pairs (n*W*H*8)."""
+    b = ctypes.c_size_t()
+    _check(lib().dis_flow_interp_workspace(n, width, height, ctypes.byref(b)))
+    return b.value
+
+
+def _interp_time(t) -> float:
+    t = float(t)
+    if not 0.0 <= t <= 1.0:  # (False for NaN)
+        raise ValueError(f"t must lie in [0, 1], not {t!r}")
+    return t
+
+
+def flow_interp(I0: np.ndarray, I1: np.ndarray, fw: np.ndarray, t: float, bw=None, return_fill: bool = False,
+                device: int = 0):
+    """The frame at time t in [0, 1] between I0 and I1 (dis_flow_interp_u8) on the
+    GPU: the forward flow fw (I0 -> I1) is projected to time t, collisions go to
+    the candidate with the lower photometric cost, and both frames are sampled
+    with the projected flow; holes are filled from I1 through bw (I1 -> I0) where
+    it is given and leads inside the frame, else with fw's own vector there.
+    I0, I1: u8 images of one shape, flow_warp's layouts; fw, bw: float32 or
+    float16 (..., H, W, 2) of one dtype and shape, read in their own dtype.
+    Returns the frame in the images' shape; return_fill: also the u8 map
+    (..., H, W): 0 = a projected vector, 1 = filled from bw, 2 = filled from fw."""
+    fl = np.asarray(fw)
+    fmt = _flow_format(fl.dtype)
+    t = _interp_time(t)
+    a, b = np.asarray(I0), np.asarray(I1)
+    if a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError(f"image dtype must be uint8, not {a.dtype} and {b.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"I0 and I1 must have one shape, not {a.shape} and {b.shape}")
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError("fw must be (H, W, 2) or (n, H, W, 2)")
+    if bw is not None:
+        bl = np.asarray(bw)
+        if bl.dtype != fl.dtype or bl.shape != fl.shape:
+            raise ValueError(f"bw must have fw's dtype and shape ({fl.dtype} {fl.shape}), not {bl.dtype} {bl.shape}")
+        bl = np.ascontiguousarray(bl)
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    if a.ndim == 2:
+        shape4 = (1,) + a.shape + (1,)
+    elif a.ndim == 3:
+        shape4 = (1,) + a.shape if a.shape[:2] == (H, W) else a.shape + (1,)
+    elif a.ndim == 4:
+        shape4 = a.shape
+    else:
+        raise ValueError("images must be (H, W), (H, W, C), (n, H, W) or (n, H, W, C)")
+    if shape4[:3] != (n, H, W):
+        raise ValueError(f"image shape {a.shape} does not match flow shape {fl.shape}")
+    C = shape4[3]
+    if C not in (1, 3, 4):
+        raise ValueError(f"images must have 1, 3 or 4 channels, not {C}")
+    a, b, fl = np.ascontiguousarray(a), np.ascontiguousarray(b), np.ascontiguousarray(fl)
+    out = np.empty(a.shape, np.uint8)
+    fill = np.empty(fl.shape[:-1], np.uint8) if return_fill else None
+    _check(lib().dis_flow_interp_u8(_ptr(a), _ptr(b), 0, 0, C, _ptr(fl), _ptr(bl) if bw is not None else None, fmt,
+                                    n, W, H, t, _ptr(out), _ptr(fill) if return_fill else None, None, MEM_HOST,
+                                    None, device))
+    return (out, fill) if return_fill else out
+
+
+def flow_interp_device(I0_ptr: int, I1_ptr: int, fw_ptr: int, flow_dtype, n: int, width: int, height: int,
+                       channels: int, t: float, dst_ptr: int, workspace_ptr: int, bw_ptr: int = 0, fill_ptr: int = 0,
+                       stride: int = 0, image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_flow_interp_u8 on raw device pointers, asynchronous on `stream`;
+    workspace_ptr: flow_interp_workspace(n, width, height) bytes, 8-byte aligned."""
+    fmt, t = _flow_format(flow_dtype), _interp_time(t)
+    _check(lib().dis_flow_interp_u8(I0_ptr, I1_ptr, stride, image_stride, channels, fw_ptr, bw_ptr or None, fmt, n,
+                                    width, height, t, dst_ptr, fill_ptr or None, workspace_ptr or None, MEM_DEVICE,
+                                    stream or None, device))
 
 
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
@@ -594,6 +673,15 @@ class DenseInverseSearch:
             wfw, wbw = flow_convert(fw, np.float32, self.device), flow_convert(bw, np.float32, self.device)
         return (fw, bw, flow_consistency(wfw, wbw, alpha1, alpha2, device=self.device),
                 flow_consistency(wbw, wfw, alpha1, alpha2, device=self.device))
+
+    def interpolate(self, I0: np.ndarray, I1: np.ndarray, ts, return_fill: bool = False):
+        """The frames between u8 H x W frames I0 and I1 at every time of `ts`
+        (each in [0, 1]): one calc_bidir, then one flow_interp per time with both
+        flows in the engine's flow_dtype as they are (no conversion). Returns the
+        list of frames; return_fill: the list of (frame, fill) pairs."""
+        ts = [_interp_time(t) for t in ts]  # raises before any device call
+        fw, bw = self.calc_bidir(I0, I1)
+        return [flow_interp(I0, I1, fw, t, bw=bw, return_fill=return_fill, device=self.device) for t in ts]
 
     def calc_bidir_device(self, n: int, I0_ptr: int, I1_ptr: int, fw_ptr: int, bw_ptr: int, stream: int = 0,
                           stride: int = 0, pair_stride: int = 0) -> None:
