@@ -1,0 +1,120 @@
+// dis_args.h -- the argument rules of the C-ABI that need nothing but integers:
+// sizes, strides, byte extents and which buffers may share memory. Host-only
+// and pure (no HIP, no allocation, nothing dereferenced; addresses are
+// uintptr_t): tests/cpp/args_host.cpp runs them under the host sanitizers.
+// Each rule returns nullptr if the call may go ahead, else what is wrong.
+#pragma once
+
+#include <limits.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <initializer_list>
+
+namespace dis {
+
+constexpr int kMaxExactSide = 1 << 24;        // pixel coordinates up to here are exact floats
+constexpr long long kMaxKeyPixels = 1ll << 31;  // interpolation: a source index fills the low half of a key
+
+inline const char* check_dims(int n, int width, int height, int max_side = INT_MAX, long long max_pixels = LLONG_MAX)
+{
+    if (n < 1 || width < 1 || height < 1) return "n, width, height must be >= 1";
+    if (width > max_side || height > max_side) return "width or height too large";
+    if ((long long)width * height > max_pixels) return "width * height too large";
+    return nullptr;
+}
+
+// A stack of n strided images (warp, interpolation); a stride of 0 means tight.
+// `bytes` ends with the last sample: the padding after the last row or image is
+// not part of the source. The limits keep every product below 2^63.
+struct ImageStack {
+    size_t stride, image_stride, bytes;
+};
+inline const char* check_image_stack(int width, int height, int channels, int n, size_t stride, size_t image_stride,
+                                     ImageStack* out)
+{
+    if (n < 1 || width < 1 || height < 1 || channels < 1) return "n, width, height, channels must be >= 1";
+    const size_t row = (size_t)width * channels;
+    if (!stride) stride = row;
+    if (stride < row) return "stride smaller than a row";
+    if (stride > (size_t(1) << 48) / (size_t)height) return "stride too large";
+    if (!image_stride) image_stride = stride * height;
+    if (image_stride < stride * height) return "image_stride smaller than an image";
+    if (image_stride > (size_t(1) << 62) / (size_t)n) return "image_stride too large";
+    *out = {stride, image_stride, (n - 1) * image_stride + (height - 1) * stride + row};
+    return nullptr;
+}
+
+// The frame batch of the calc entry points: n pairs of W x H bytes, frame k of
+// either role at k * pair_stride (which a single pair does not need).
+struct FrameBatch {
+    size_t stride, pair_stride, bytes;
+};
+inline const char* check_frame_batch(int W, int H, int n, int max_batch, size_t stride, size_t pair_stride,
+                                     FrameBatch* out)
+{
+    if (n < 1 || n > max_batch) return "n must be in [1, max_batch]";
+    if (!stride) stride = (size_t)W;
+    if (stride < (size_t)W) return "stride < width";
+    if (!pair_stride) pair_stride = stride * H;
+    if (n > 1 && pair_stride < stride * H) return "pair_stride too small";
+    *out = {stride, pair_stride, (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W};
+    return nullptr;
+}
+
+// [a, a + na) and [b, b + nb) share a byte (empty ranges share none; the sums
+// are formed so that a range ending at the top of the address space does not
+// wrap)
+inline bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb)
+{
+    if (na == 0 || nb == 0) return false;
+    return a <= b ? b - a < na : a - b < nb;
+}
+
+// Of n named ranges, the first nin are inputs and the others outputs: every
+// output must be disjoint from every input and from every other output (an
+// absent buffer is an empty range). The first offending pair, by name.
+struct NamedRange {
+    uintptr_t p;
+    size_t bytes;
+    const char* name;
+};
+struct PairMessage {
+    char text[64];
+};
+inline bool first_overlap(const NamedRange* r, int nin, int n, int* a, int* b)
+{
+    for (int o = nin; o < n; ++o)
+        for (int k = 0; k < n; ++k)  // every input, then the outputs after this one
+            if ((k < nin || k > o) && ranges_overlap(r[o].p, r[o].bytes, r[k].p, r[k].bytes)) {
+                *a = o, *b = k;
+                return true;
+            }
+    return false;
+}
+inline const char* check_disjoint(const NamedRange* r, int nin, int n, PairMessage* why)
+{
+    int a, b;
+    if (!first_overlap(r, nin, n, &a, &b)) return nullptr;
+    size_t k = 0;  // "<a> and <b> overlap", cut to fit
+    for (const char* part : {r[a].name, " and ", r[b].name, " overlap"})
+        for (; *part && k + 1 < sizeof why->text; ++part) why->text[k++] = *part;
+    why->text[k] = 0;
+    return why->text;
+}
+
+// A warm-started call (dis_calc_batch_init_u8): `init` may start exactly where
+// `flow` starts (flow in, flow out: the init plane is complete before any
+// output is written), otherwise the two must be disjoint; `init` must not
+// touch either frame batch.
+inline const char* check_init_aliasing(uintptr_t init, size_t init_bytes, uintptr_t flow, size_t flow_bytes,
+                                       uintptr_t i0, uintptr_t i1, size_t frame_bytes)
+{
+    if (init != flow && ranges_overlap(init, init_bytes, flow, flow_bytes))
+        return "init partially overlaps flow (it may be the flow buffer itself, or disjoint from it)";
+    if (ranges_overlap(init, init_bytes, i0, frame_bytes) || ranges_overlap(init, init_bytes, i1, frame_bytes))
+        return "init overlaps the frames";
+    return nullptr;
+}
+
+}  // namespace dis

@@ -1,0 +1,204 @@
+// dis_flowops.hip -- the entry points of the C-ABI that need no context. Each
+// is the pure argument rules (dis_args.h) and its own value checks, all before
+// the first HIP call; then the device; then the launch, staged (dis_stage.h)
+// when the pointers are the host's.
+#include <cmath>
+#include <cstring>
+
+#include "dis_args.h"
+#include "dis_kernels.h"
+#include "dis_stage.h"
+
+namespace {
+
+bool bad_mem(dis_mem where) { return where != DIS_MEM_HOST && where != DIS_MEM_DEVICE; }
+bool bad_format(int f) { return f != DIS_FLOW_F32 && f != DIS_FLOW_F16; }
+uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+}  // namespace
+
+extern "C" {
+
+dis_status dis_flow_color(const float* flow, int n, int width, int height, float maxmotion, uint8_t* bgr,
+                          dis_mem where, void* stream, int device)
+{
+    if (!flow || !bgr) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height));
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t px = (size_t)width * height * n;
+    const size_t ws_bytes = sizeof(unsigned int) * dis::flow_color_ws_words(n);
+    if (where == DIS_MEM_DEVICE) {
+        unsigned int* maxbits = nullptr;
+        DIS_HIP(hipMallocAsync(reinterpret_cast<void**>(&maxbits), ws_bytes, s));
+        const hipError_t e = dis::launch_flow_color(flow, n, width, height, maxmotion, bgr, maxbits, s);
+        DIS_HIP(hipFreeAsync(maxbits, s));
+        DIS_HIP(e);
+        return DIS_OK;
+    }
+    dis::HostStage st(s);
+    const float* dflow = st.in(flow, sizeof(float) * 2 * px);
+    uint8_t* dbgr = st.out(bgr, 3 * px);
+    unsigned int* maxbits = static_cast<unsigned int*>(st.scratch(ws_bytes));
+    return st.finish([&] { return dis::launch_flow_color(dflow, n, width, height, maxmotion, dbgr, maxbits, s); },
+                     "flow colour coding");
+}
+
+dis_status dis_flow_convert(const void* src, int src_format, void* dst, int dst_format, size_t count, dis_mem where,
+                            void* stream, int device)
+{
+    if (!src || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (bad_format(src_format) || bad_format(dst_format))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "formats must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    const size_t ssz = src_format == DIS_FLOW_F16 ? 2 : 4, dsz = dst_format == DIS_FLOW_F16 ? 2 : 4;
+    if (count > (size_t(1) << 40)) return fail(DIS_ERR_INVALID_ARGUMENT, "count too large");
+    const dis::NamedRange r[2] = {{addr(src), count * ssz, "src"}, {addr(dst), count * dsz, "dst"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 1, 2, &why));
+    if (where == DIS_MEM_DEVICE && ((r[0].p & (ssz - 1)) || (r[1].p & (dsz - 1))))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers must be aligned to their element (4 / 2 bytes)");
+    if (!count) return DIS_OK;
+    if (where == DIS_MEM_HOST && src_format == dst_format) {  // a host copy needs no device
+        std::memcpy(dst, src, r[0].bytes);
+        return DIS_OK;
+    }
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (where == DIS_MEM_DEVICE) {
+        if (src_format == dst_format)
+            DIS_HIP(hipMemcpyAsync(dst, src, r[0].bytes, hipMemcpyDeviceToDevice, s));
+        else
+            DIS_HIP(dis::launch_flow_convert(src, src_format, dst, count, s));
+        return DIS_OK;
+    }
+    dis::HostStage st(s);
+    const void* dsrc = st.in(src, r[0].bytes);
+    void* ddst = st.out(dst, r[1].bytes);
+    return st.finish([&] { return dis::launch_flow_convert(dsrc, src_format, ddst, count, s); }, "flow conversion");
+}
+
+dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int width, int height, float alpha1,
+                                float alpha2, uint8_t* mask, float* err, dis_mem where, void* stream, int device)
+{
+    if (!fw || !bw || !mask) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide));
+    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0.0f || alpha2 < 0.0f)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "alpha1 and alpha2 must be finite and >= 0");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    if (dis::flow_consistency_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    if (where == DIS_MEM_DEVICE && (((addr(fw) | addr(bw)) & 7) || (addr(err) & 3)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be 8-byte aligned, err 4-byte aligned");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t px = (size_t)width * height * n;
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const float* dfw = st.in(fw, sizeof(float) * 2 * px);
+    const float* dbw = st.in(bw, sizeof(float) * 2 * px);
+    uint8_t* dmask = st.out(mask, px);
+    float* derr = st.out(err, sizeof(float) * px);
+    return st.finish(
+        [&] { return dis::launch_flow_consistency(dfw, dbw, n, width, height, alpha1, alpha2, dmask, derr, s); },
+        "flow consistency check");
+}
+
+dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                            const void* flow, int flow_format, int n, int width, int height, float scale, int border,
+                            uint8_t* dst, uint8_t* valid, dis_mem where, void* stream, int device)
+{
+    if (!src || !flow || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide));
+    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
+    if (bad_format(flow_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (border != DIS_BORDER_REPLICATE && border != DIS_BORDER_ZERO)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "border must be DIS_BORDER_REPLICATE or DIS_BORDER_ZERO");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!std::isfinite(scale) || std::fabs(scale) > 1024.0f)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "scale must be finite with |scale| <= 1024");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    // (it also keeps every byte count below far under 2^63)
+    if (dis::flow_warp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    dis::ImageStack im;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, src_stride, src_image_stride, &im));
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    const dis::NamedRange r[4] = {{addr(src), im.bytes, "src"}, {addr(flow), px * fsz, "flow"},
+                                  {addr(dst), px * channels, "dst"}, {addr(valid), valid ? px : 0, "valid"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 2, 4, &why));
+    if (where == DIS_MEM_DEVICE && (addr(flow) & (fsz - 1)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int f16 = flow_format == DIS_FLOW_F16, zero = border == DIS_BORDER_ZERO;
+    // a host source is staged as it lies (rows and images keep their strides)
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const uint8_t* dsrc = st.in(src, im.bytes);
+    const void* dflow = st.in(flow, px * fsz);
+    uint8_t* ddst = st.out(dst, px * channels);
+    uint8_t* dvalid = st.out(valid, px);
+    return st.finish([&] { return dis::launch_flow_warp(dsrc, im.stride, im.image_stride, channels, dflow, f16, n, width,
+                                                        height, scale, zero, ddst, dvalid, s); }, "flow warp");
+}
+
+dis_status dis_flow_interp_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide, dis::kMaxKeyPixels));
+    if (dis::flow_interp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    *bytes = sizeof(uint64_t) * (size_t)width * height * n;
+    return DIS_OK;
+}
+
+dis_status dis_flow_interp_u8(const uint8_t* I0, const uint8_t* I1, size_t stride_in, size_t image_stride_in, int channels,
+                              const void* fw, const void* bw, int flow_format, int n, int width, int height, float t,
+                              uint8_t* dst, uint8_t* fill, void* workspace, dis_mem where, void* stream, int device)
+{
+    if (!I0 || !I1 || !fw || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide, dis::kMaxKeyPixels));
+    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
+    if (bad_format(flow_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!(t >= 0.0f && t <= 1.0f)) return fail(DIS_ERR_INVALID_ARGUMENT, "t must lie in [0, 1]");  // also NaN
+    // the splat folds n * W * H pixels into a one-dimensional grid: its size is the only limit on n
+    // (it also keeps every byte count below far under 2^63)
+    if (dis::flow_interp_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    dis::ImageStack im;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, stride_in, image_stride_in, &im));
+    const bool dev = where == DIS_MEM_DEVICE;
+    if (dev && !workspace) return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers need a workspace");
+    if (dev && (addr(workspace) & 7)) return fail(DIS_ERR_INVALID_ARGUMENT, "workspace must be 8-byte aligned");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    // (a null bw, a null fill and a host call's workspace take no part)
+    const dis::NamedRange r[7] = {{addr(I0), im.bytes, "I0"}, {addr(I1), im.bytes, "I1"}, {addr(fw), px * fsz, "fw"},
+                                  {addr(bw), bw ? px * fsz : 0, "bw"}, {addr(dst), px * channels, "dst"},
+                                  {addr(fill), fill ? px : 0, "fill"},
+                                  {addr(workspace), dev ? px * sizeof(uint64_t) : 0, "workspace"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 4, 7, &why));
+    if (dev && ((addr(fw) | addr(bw)) & (fsz - 1)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int f16 = flow_format == DIS_FLOW_F16;
+    // host frames are staged as they lie (rows and images keep their strides)
+    dis::HostStage st(s, !dev);
+    const uint8_t* d0 = st.in(I0, im.bytes);
+    const uint8_t* d1 = st.in(I1, im.bytes);
+    const void* dfw = st.in(fw, px * fsz);
+    const void* dbw = st.in(bw, px * fsz);
+    uint8_t* ddst = st.out(dst, px * channels);
+    uint8_t* dfill = st.out(fill, px);
+    void* dws = dev ? workspace : st.scratch(px * sizeof(uint64_t));
+    return st.finish([&] { return dis::launch_flow_interp(d0, d1, im.stride, im.image_stride, channels, dfw, dbw, f16, n,
+                                                          width, height, t, ddst, dfill, dws, s); }, "flow interpolation");
+}
+
+}  // extern "C"

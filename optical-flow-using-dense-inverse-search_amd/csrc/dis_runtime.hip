@@ -1,5 +1,7 @@
-// dis_runtime.hip -- the C-ABI (include/dis_abi.h): parameter validation,
-// geometry, device workspace and the per-batch launch sequence.
+// dis_runtime.hip -- the context of the C-ABI (include/dis_abi.h): parameter
+// validation, geometry, device workspace, the per-batch launch sequence and
+// every entry point that takes a context (the others: dis_flowops.hip). Shared
+// with that file: argument rules dis_args.h, staging dis_stage.h, dis_host.h.
 //
 // The launch sequence is the reference's control flow restated for a batch of
 // pairs resident in HBM: src/main.cpp:135-198 (pad/convert, pyramid, upsample,
@@ -20,34 +22,30 @@
 
 #include <dlfcn.h>
 
-#include "dis_alias.h"
+#include "dis_args.h"
 #include "dis_kernels.h"
 #include "dis_plan.h"
+#include "dis_stage.h"
 
-namespace {
+static thread_local std::string g_err;
 
+namespace dis {
 
-thread_local std::string g_err;
-
-dis_status fail(dis_status s, const std::string& msg)
+// error reporting of every translation unit (dis_host.h; dis_io.cpp, dis_plan.cpp)
+dis_status set_error(dis_status s, const std::string& msg)
 {
     g_err = msg;
     return s;
 }
 
-#define DIS_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(DIS_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
-
-}  // namespace
-
-namespace dis {
-
-// error reporting for the host-only translation units (dis_io.cpp)
-dis_status set_error(dis_status s, const std::string& msg) { return fail(s, msg); }
+dis_status use_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    DIS_HIP(hipSetDevice(device));
+    return DIS_OK;
+}
 
 bool make_geometry(const dis_params& p, int W, int H, Geometry* g)
 {
@@ -316,20 +314,18 @@ struct dis_ctx {
     // (0 = auto)
     std::unique_ptr<HostPipe> hp;
     int host_chunk = 0;
-    // dis_calc_bidir_batch_u8 with DIS_MEM_HOST: device staging for max_batch
-    // pairs (both frames; both flows), made on the first such call
-    uint8_t* bd_in = nullptr;
-    float2* bd_out = nullptr;
+    // dis_calc_bidir_batch_u8 and dis_calc_batch_init_u8 with DIS_MEM_HOST
+    // (synchronous calls: one at a time): device staging for max_batch pairs,
+    // both frames in stage_in and two float flows in stage_out (both
+    // directions, or the flow and the init input), made on the first such call
+    uint8_t* stage_in = nullptr;
+    float2* stage_out = nullptr;
     // warm start (dis_calc_batch_init_u8): the context's init planes, iw x ih
     // float2 per pair for max_batch pairs; `warm` is set for the duration of a
     // warm-started call's enqueue (the coarsest level then starts from them)
     float2* init = nullptr;
     int iw = 0, ih = 0;
     bool warm = false;
-    // ... and, for host pointers, device staging for max_batch pairs (frames;
-    // init input and flow), made on the first such call
-    uint8_t* wi_in = nullptr;
-    float2* wi_out = nullptr;
     // kernel timing
     int timing = 0;
     struct Rec {
@@ -385,16 +381,12 @@ void free_ws(dis_ctx* c)
     hipFree(c->vr_ws);
     c->vr_ws = nullptr;
     c->hp.reset();
-    hipFree(c->bd_in);
-    hipFree(c->bd_out);
-    c->bd_in = nullptr;
-    c->bd_out = nullptr;
+    hipFree(c->stage_in);
+    hipFree(c->stage_out);
+    c->stage_in = nullptr;
+    c->stage_out = nullptr;
     hipFree(c->init);
-    hipFree(c->wi_in);
-    hipFree(c->wi_out);
     c->init = nullptr;
-    c->wi_in = nullptr;
-    c->wi_out = nullptr;
     c->img0 = c->img1 = c->dx = c->dy = nullptr;
     c->pu = c->dense = nullptr;
 }
@@ -1292,6 +1284,56 @@ dis::DensifyArgs densify_level(const dis::Geometry& g, int l, float2* pu, float2
     return d;
 }
 
+// The frame arguments of the three batch entry points; resolves the strides.
+// What needs no context comes first: checked the same with or without a device.
+dis_status check_frames(const dis_ctx* c, int n, const void* I0, const void* I1, const void* flow_a,
+                        const void* flow_b, dis_mem where, size_t stride, size_t pair_stride, dis::FrameBatch* fb)
+{
+    if (!I0 || !I1 || !flow_a || !flow_b) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
+    if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    DIS_ARG(dis::check_frame_batch(c->g.W, c->g.H, n, c->max_batch, stride, pair_stride, fb));
+    return DIS_OK;
+}
+
+// A bidirectional or warm-started call on host pointers: synchronous, staged
+// through device buffers for max_batch pairs made on the first such call (the
+// chunked pipeline of dis_calc_batch_u8 is not used here). The frames go up
+// tightly packed, and `up_b` (if any) into the second of two output slots, each
+// sized for a batch of float flows and serving either format; `enqueue` runs on
+// them on the context's own stream; slot a comes down to `down_a`, b to `down_b`.
+template <class Enqueue>
+dis_status staged_call(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, const dis::FrameBatch& fb,
+                       const void* up_b, size_t up_bytes, void* down_a, void* down_b, size_t down_bytes,
+                       Enqueue&& enqueue)
+{
+    const int W = c->g.W, H = c->g.H;
+    const size_t fpp = (size_t)W * H, B = (size_t)c->max_batch;
+    if ((!c->stage_in && hipMalloc(&c->stage_in, 2 * fpp * B) != hipSuccess) ||
+        (!c->stage_out && hipMalloc(&c->stage_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(DIS_ERR_OUT_OF_MEMORY, "host-path device buffer allocation failed");
+    }
+    const hipStream_t s = c->own;
+    uint8_t *const d0 = c->stage_in, *const d1 = d0 + fpp * B;
+    float2 *const da = c->stage_out, *const db = da + fpp * B;
+    for (int k = 0; k < n; ++k) {
+        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
+        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
+    }
+    if (up_b) DIS_HIP(hipMemcpyAsync(db, up_b, up_bytes, hipMemcpyHostToDevice, s));
+    const dis_status st = enqueue(d0, d1, (size_t)W, fpp, da, db, s);
+    if (st != DIS_OK) {
+        (void)hipStreamSynchronize(s);
+        return st;
+    }
+    DIS_HIP(hipMemcpyAsync(down_a, da, down_bytes, hipMemcpyDeviceToHost, s));
+    if (down_b) DIS_HIP(hipMemcpyAsync(down_b, db, down_bytes, hipMemcpyDeviceToHost, s));
+    DIS_HIP(hipStreamSynchronize(s));
+    return DIS_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1396,10 +1438,7 @@ dis_status dis_create(dis_ctx** out, const dis_params* params, int width, int he
     dis_status st = check_params(params, width, height);
     if (st != DIS_OK) return st;
     if (max_batch < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "max_batch must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
+    if (dis_status ds = dis::use_device(device)) return ds;
     dis_ctx* c = new (std::nothrow) dis_ctx();
     if (!c) return fail(DIS_ERR_OUT_OF_MEMORY, "host allocation failed");
     c->p = *params;
@@ -1408,10 +1447,6 @@ dis_status dis_create(dis_ctx** out, const dis_params* params, int width, int he
     if (!dis::make_geometry(*params, width, height, &c->g)) {
         delete c;
         return fail(DIS_ERR_INVALID_ARGUMENT, "bad geometry");
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        delete c;
-        return fail(DIS_ERR_DEVICE, "hipSetDevice failed");
     }
     const dis::Geometry& g = c->g;
     const size_t B = (size_t)max_batch;
@@ -1451,14 +1486,7 @@ dis_status dis_create(dis_ctx** out, const dis_params* params, int width, int he
     // sub-batches (measured: 20.1k -> 15.5k pairs/s at 1080p MEDIUM).
     if (ok) ok = hipStreamCreateWithFlags(&c->cap, hipStreamNonBlocking) == hipSuccess;
     if (!ok) {
-        free_ws(c);
-        for (int k = 0; k < dis_ctx::kMaxSub; ++k)
-            if (c->join[k]) hipEventDestroy(c->join[k]);
-        if (c->fork) hipEventDestroy(c->fork);
-        if (c->done) hipEventDestroy(c->done);
-        if (c->cap) hipStreamDestroy(c->cap);
-        if (c->own) hipStreamDestroy(c->own);
-        delete c;
+        dis_destroy(c);  // (whatever was made so far)
         return fail(DIS_ERR_OUT_OF_MEMORY, "device workspace allocation failed");
     }
     *out = c;
@@ -1496,23 +1524,16 @@ dis_status dis_destroy(dis_ctx* c)
 dis_status dis_calc_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, size_t stride,
                              size_t pair_stride, float* flow, dis_mem where, void* stream)
 {
-    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!I0 || !I1 || !flow) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
-    if (n < 1 || n > c->max_batch) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
-    const int W = c->g.W, H = c->g.H;
-    if (stride == 0) stride = (size_t)W;
-    if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
-    if (pair_stride == 0) pair_stride = stride * H;
-    if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
+    dis::FrameBatch fb;
+    if (dis_status st = check_frames(c, n, I0, I1, flow, flow, where, stride, pair_stride, &fb)) return st;
     if (where == DIS_MEM_DEVICE && c->f16() && (reinterpret_cast<uintptr_t>(flow) & 3))
         return fail(DIS_ERR_INVALID_ARGUMENT, "DIS_FLOW_F16: flow must be 4-byte aligned");
     DIS_HIP(hipSetDevice(c->device));
     if (where == DIS_MEM_DEVICE) {
-        return run_batches_graph(c, n, I0, I1, stride, pair_stride, reinterpret_cast<float2*>(flow),
+        return run_batches_graph(c, n, I0, I1, fb.stride, fb.pair_stride, reinterpret_cast<float2*>(flow),
                                  reinterpret_cast<hipStream_t>(stream));
     }
-    if (where != DIS_MEM_HOST) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    return calc_host(c, n, I0, I1, stride, pair_stride, flow);
+    return calc_host(c, n, I0, I1, fb.stride, fb.pair_stride, flow);
 }
 
 // Both directions in one call: always the eager enqueue (never the main graph
@@ -1521,64 +1542,27 @@ dis_status dis_calc_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
 dis_status dis_calc_bidir_batch_u8(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, size_t stride,
                                    size_t pair_stride, float* flow_fw, float* flow_bw, dis_mem where, void* stream)
 {
-    // (what needs no context first: checked the same with or without a device)
-    if (!I0 || !I1 || !flow_fw || !flow_bw) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
-    if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
-    if (flow_fw == flow_bw) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (n > c->max_batch) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
-    const int W = c->g.W, H = c->g.H;
-    if (stride == 0) stride = (size_t)W;
-    if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
-    if (pair_stride == 0) pair_stride = stride * H;
-    if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
-    const size_t fpp = (size_t)W * H;  // (u, v) vectors per pair
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(flow_fw), b0 = reinterpret_cast<uintptr_t>(flow_bw);
+    dis::FrameBatch fb;  // (what needs no context is refused first, this call's own such rule included)
+    if (flow_fw && flow_fw == flow_bw) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
+    if (dis_status st = check_frames(c, n, I0, I1, flow_fw, flow_bw, where, stride, pair_stride, &fb)) return st;
+    const size_t fpp = (size_t)c->g.W * c->g.H;  // (u, v) vectors per pair
     const size_t fbytes = c->vec_bytes() * fpp * (size_t)n;  // in the context's flow format
-    if (a0 < b0 + fbytes && b0 < a0 + fbytes)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_fw and flow_bw overlap");
-    if (where == DIS_MEM_DEVICE && c->f16() && ((a0 | b0) & 3))
+    const dis::NamedRange out[2] = {{reinterpret_cast<uintptr_t>(flow_fw), fbytes, "flow_fw"},
+                                    {reinterpret_cast<uintptr_t>(flow_bw), fbytes, "flow_bw"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(out, 0, 2, &why));
+    if (where == DIS_MEM_DEVICE && c->f16() && ((out[0].p | out[1].p) & 3))
         return fail(DIS_ERR_INVALID_ARGUMENT, "DIS_FLOW_F16: flow_fw and flow_bw must be 4-byte aligned");
     DIS_HIP(hipSetDevice(c->device));
-    if (where == DIS_MEM_DEVICE) {
+    auto enqueue = [&](const uint8_t* f0, const uint8_t* f1, size_t st, size_t pst, float2* fw, float2* bw,
+                       hipStream_t s) {
         std::lock_guard<std::mutex> lock(pool_mutex(c->device));  // eager enqueue onto the pooled streams
-        return run_batches(c, n, I0, I1, stride, pair_stride, reinterpret_cast<float2*>(flow_fw),
-                           reinterpret_cast<hipStream_t>(stream), false, reinterpret_cast<float2*>(flow_bw));
-    }
-    // host memory: synchronous, staged through device buffers for max_batch
-    // pairs made on the first such call (the chunked pipeline of
-    // dis_calc_batch_u8 is not used here); the output staging is sized for
-    // float flows and serves either format
-    const size_t B = (size_t)c->max_batch;
-    if (!c->bd_in || !c->bd_out) {
-        if ((!c->bd_in && hipMalloc(&c->bd_in, 2 * fpp * B) != hipSuccess) ||
-            (!c->bd_out && hipMalloc(&c->bd_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
-            (void)hipGetLastError();
-            return fail(DIS_ERR_OUT_OF_MEMORY, "bidirectional host-path device buffer allocation failed");
-        }
-    }
-    const hipStream_t s = c->own;
-    uint8_t* const d0 = c->bd_in;
-    uint8_t* const d1 = c->bd_in + fpp * B;
-    float2* const dfw = c->bd_out;
-    float2* const dbw = c->bd_out + fpp * B;
-    for (int k = 0; k < n; ++k) {
-        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
-        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
-    }
-    {
-        std::lock_guard<std::mutex> lock(pool_mutex(c->device));
-        dis_status st = run_batches(c, n, d0, d1, (size_t)W, fpp, dfw, s, false, dbw);
-        if (st != DIS_OK) {
-            (void)hipStreamSynchronize(s);
-            return st;
-        }
-    }
-    DIS_HIP(hipMemcpyAsync(flow_fw, dfw, fbytes, hipMemcpyDeviceToHost, s));
-    DIS_HIP(hipMemcpyAsync(flow_bw, dbw, fbytes, hipMemcpyDeviceToHost, s));
-    DIS_HIP(hipStreamSynchronize(s));
-    return DIS_OK;
+        return run_batches(c, n, f0, f1, st, pst, fw, s, false, bw);
+    };
+    if (where == DIS_MEM_DEVICE)
+        return enqueue(I0, I1, fb.stride, fb.pair_stride, reinterpret_cast<float2*>(flow_fw),
+                       reinterpret_cast<float2*>(flow_bw), reinterpret_cast<hipStream_t>(stream));
+    return staged_call(c, n, I0, I1, fb, nullptr, 0, flow_fw, flow_bw, fbytes, enqueue);
 }
 
 dis_status dis_init_plane_size(dis_ctx* c, int* iw, int* ih)
@@ -1597,31 +1581,18 @@ dis_status dis_flow_to_init(dis_ctx* c, int n, const float* flow, float* init_pl
     if (n < 1 || n > 65535) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, 65535]");
     if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
     if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (where == DIS_MEM_DEVICE &&
+        (reinterpret_cast<uintptr_t>(flow) & (c->f16() ? 3 : 7) || reinterpret_cast<uintptr_t>(init_planes) & 7))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow and init_planes must be 8-byte aligned (a DIS_FLOW_F16 flow: 4-byte)");
     DIS_HIP(hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (where == DIS_MEM_DEVICE) {
-        if (reinterpret_cast<uintptr_t>(flow) & (c->f16() ? 3 : 7) || reinterpret_cast<uintptr_t>(init_planes) & 7)
-            return fail(DIS_ERR_INVALID_ARGUMENT,
-                        "flow and init_planes must be 8-byte aligned (a DIS_FLOW_F16 flow: 4-byte)");
-        DIS_HIP(dis::launch_flow_to_init(flow, init_planes, n, c->g, s, {}, c->f16()));
-        return DIS_OK;
-    }
     const size_t fbytes = c->vec_bytes() * (size_t)c->g.W * c->g.H * n;  // in the context's flow format
     const size_t pbytes = sizeof(float2) * (size_t)c->iw * c->ih * n;
-    float *dflow = nullptr, *dplanes = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&dflow, fbytes) != hipSuccess || hipMalloc(&dplanes, pbytes) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(dflow, flow, fbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_to_init(dflow, dplanes, n, c->g, s, {}, c->f16()) != hipSuccess ||
-               hipMemcpyAsync(init_planes, dplanes, pbytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow to init plane reduction failed");
-    }
-    hipFree(dflow);
-    hipFree(dplanes);
-    return rc;
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const float* dflow = st.in(flow, fbytes);
+    float* dplanes = st.out(init_planes, pbytes);
+    return st.finish([&] { return dis::launch_flow_to_init(dflow, dplanes, n, c->g, s, {}, c->f16()); },
+                     "flow to init plane reduction");
 }
 
 // Warm start: fill the context's init planes from `init` (the reduction or the
@@ -1634,29 +1605,17 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
                                   void* stream)
 {
     if (!init) return dis_calc_batch_u8(c, n, I0, I1, stride, pair_stride, flow, where, stream);
-    // (what needs no context first: checked the same with or without a device)
-    if (!I0 || !I1 || !flow) return fail(DIS_ERR_INVALID_ARGUMENT, "null frame or flow pointer");
-    if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
+    dis::FrameBatch fb;  // (what needs no context is refused first, this call's own such rule included)
     if (init_kind != DIS_INIT_COARSE && init_kind != DIS_INIT_FULLRES)
         return fail(DIS_ERR_INVALID_ARGUMENT, "init_kind must be DIS_INIT_COARSE or DIS_INIT_FULLRES");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (n > c->max_batch) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
-    const int W = c->g.W, H = c->g.H;
-    if (stride == 0) stride = (size_t)W;
-    if (stride < (size_t)W) return fail(DIS_ERR_INVALID_ARGUMENT, "stride < width");
-    if (pair_stride == 0) pair_stride = stride * H;
-    if (n > 1 && pair_stride < stride * H) return fail(DIS_ERR_INVALID_ARGUMENT, "pair_stride too small");
-    const size_t fpp = (size_t)W * H;                 // (u, v) vectors per flow
-    const size_t ipp = (size_t)c->iw * c->ih;         // float2 per init plane
+    if (dis_status st = check_frames(c, n, I0, I1, flow, flow, where, stride, pair_stride, &fb)) return st;
+    const size_t fpp = (size_t)c->g.W * c->g.H;       // (u, v) vectors per flow
+    const size_t ipp = (size_t)c->iw * c->ih;         // float2 per init plane (ipp <= fpp: never larger than a flow)
     const size_t fbytes = c->vec_bytes() * fpp * (size_t)n;  // in the context's flow format (FULLRES init too)
     const size_t ibytes = init_kind == DIS_INIT_FULLRES ? fbytes : sizeof(float2) * ipp * (size_t)n;
-    const size_t frame_bytes = (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W;
-    if (const char* why = dis::check_init_aliasing(reinterpret_cast<uintptr_t>(init), ibytes,
-                                                   reinterpret_cast<uintptr_t>(flow), fbytes,
-                                                   reinterpret_cast<uintptr_t>(I0), reinterpret_cast<uintptr_t>(I1),
-                                                   frame_bytes))
-        return fail(DIS_ERR_INVALID_ARGUMENT, why);
+    DIS_ARG(dis::check_init_aliasing(reinterpret_cast<uintptr_t>(init), ibytes, reinterpret_cast<uintptr_t>(flow),
+                                     fbytes, reinterpret_cast<uintptr_t>(I0), reinterpret_cast<uintptr_t>(I1),
+                                     fb.bytes));
     const bool init_f16 = c->f16() && init_kind == DIS_INIT_FULLRES;
     if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(init) & (init_f16 ? 3 : 7)))
         return fail(DIS_ERR_INVALID_ARGUMENT, "init must be 8-byte aligned (a DIS_FLOW_F16 flow: 4-byte)");
@@ -1667,8 +1626,9 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
     // forks from `s` after the fill, so the planes are complete -- and `init`
     // has been read to the end -- before any kernel of the chain starts, the
     // one that writes `flow` included. That is what lets init be flow.
-    auto enqueue = [&](const uint8_t* f0, const uint8_t* f1, size_t st, size_t pst, const float* in, float2* out,
+    auto enqueue = [&](const uint8_t* f0, const uint8_t* f1, size_t st, size_t pst, float2* out, const void* init_in,
                        hipStream_t s) -> dis_status {
+        const float* in = static_cast<const float*>(init_in);
         if (c->needs_wait(s)) DIS_HIP(hipStreamWaitEvent(s, c->done, 0));  // the planes are workspace
         if (init_kind == DIS_INIT_FULLRES)
             DIS_HIP(dis::launch_flow_to_init(in, reinterpret_cast<float*>(c->init), n, c->g, s, timing(c, 6),
@@ -1683,38 +1643,9 @@ dis_status dis_calc_batch_init_u8(dis_ctx* c, int n, const uint8_t* I0, const ui
         return r;
     };
     if (where == DIS_MEM_DEVICE)
-        return enqueue(I0, I1, stride, pair_stride, init, reinterpret_cast<float2*>(flow),
+        return enqueue(I0, I1, fb.stride, fb.pair_stride, reinterpret_cast<float2*>(flow), init,
                        reinterpret_cast<hipStream_t>(stream));
-    // host memory: synchronous, staged through device buffers for max_batch
-    // pairs made on the first such call (the chunked pipeline of
-    // dis_calc_batch_u8 is not used here); the flow and init staging is sized
-    // for float flows and serves either format
-    const size_t B = (size_t)c->max_batch;
-    if (!c->wi_in || !c->wi_out) {
-        if ((!c->wi_in && hipMalloc(&c->wi_in, 2 * fpp * B) != hipSuccess) ||
-            (!c->wi_out && hipMalloc(&c->wi_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
-            (void)hipGetLastError();
-            return fail(DIS_ERR_OUT_OF_MEMORY, "warm-start host-path device buffer allocation failed");
-        }
-    }
-    const hipStream_t s = c->own;
-    uint8_t* const d0 = c->wi_in;
-    uint8_t* const d1 = c->wi_in + fpp * B;
-    float2* const dflow = c->wi_out;
-    float2* const dinit = c->wi_out + fpp * B;  // (ipp <= fpp: a plane is never larger than a flow)
-    for (int k = 0; k < n; ++k) {
-        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
-        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + (size_t)k * pair_stride, stride, W, H, hipMemcpyHostToDevice, s));
-    }
-    DIS_HIP(hipMemcpyAsync(dinit, init, ibytes, hipMemcpyHostToDevice, s));
-    const dis_status st = enqueue(d0, d1, (size_t)W, fpp, reinterpret_cast<const float*>(dinit), dflow, s);
-    if (st != DIS_OK) {
-        (void)hipStreamSynchronize(s);
-        return st;
-    }
-    DIS_HIP(hipMemcpyAsync(flow, dflow, fbytes, hipMemcpyDeviceToHost, s));
-    DIS_HIP(hipStreamSynchronize(s));
-    return DIS_OK;
+    return staged_call(c, n, I0, I1, fb, init, ibytes, flow, nullptr, fbytes, enqueue);
 }
 
 dis_status dis_set_host_pipeline(dis_ctx* c, int chunk_pairs)
@@ -1951,10 +1882,7 @@ dis_status dis_flow_from_pyramids(const float* const* img_first, const float* co
         poff[l] = tot;
         tot += (long long)(g.lv[l].W + 2 * img_padding) * (g.lv[l].H + 2 * img_padding);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
+    if (dis_status ds = dis::use_device(device)) return ds;
     // per-device workspace, grown on demand and kept for the next call (the
     // reference constructs one OpticalFlowClass per frame pair: a malloc/free
     // per call would dominate)
@@ -2064,335 +1992,6 @@ dis_status dis_flow_from_pyramids(const float* const* img_first, const float* co
         hipStreamSynchronize(s) != hipSuccess)
         return fail(DIS_ERR_DEVICE, "result download failed");
     return DIS_OK;
-}
-
-dis_status dis_flow_color(const float* flow, int n, int width, int height, float maxmotion, uint8_t* bgr,
-                          dis_mem where, void* stream, int device)
-{
-    if (!flow || !bgr) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t fbytes = sizeof(float) * 2 * (size_t)width * height * n;
-    const size_t cbytes = (size_t)3 * width * height * n;
-    if (where == DIS_MEM_DEVICE) {
-        unsigned int* maxbits = nullptr;
-        DIS_HIP(hipMallocAsync(reinterpret_cast<void**>(&maxbits), sizeof(unsigned int) * dis::flow_color_ws_words(n), s));
-        const hipError_t e = dis::launch_flow_color(flow, n, width, height, maxmotion, bgr, maxbits, s);
-        DIS_HIP(hipFreeAsync(maxbits, s));
-        DIS_HIP(e);
-        return DIS_OK;
-    }
-    float* dflow = nullptr;
-    uint8_t* dbgr = nullptr;
-    unsigned int* maxbits = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&dflow, fbytes) != hipSuccess || hipMalloc(&dbgr, cbytes) != hipSuccess ||
-        hipMalloc(&maxbits, sizeof(unsigned int) * dis::flow_color_ws_words(n)) != hipSuccess) {
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(dflow, flow, fbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_color(dflow, n, width, height, maxmotion, dbgr, maxbits, s) != hipSuccess ||
-               hipMemcpyAsync(bgr, dbgr, cbytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow colour coding failed");
-    }
-    hipFree(dflow);
-    hipFree(dbgr);
-    hipFree(maxbits);
-    return rc;
-}
-
-dis_status dis_flow_convert(const void* src, int src_format, void* dst, int dst_format, size_t count, dis_mem where,
-                            void* stream, int device)
-{
-    if (!src || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if ((src_format != DIS_FLOW_F32 && src_format != DIS_FLOW_F16) ||
-        (dst_format != DIS_FLOW_F32 && dst_format != DIS_FLOW_F16))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "formats must be DIS_FLOW_F32 or DIS_FLOW_F16");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    const size_t ssz = src_format == DIS_FLOW_F16 ? 2 : 4, dsz = dst_format == DIS_FLOW_F16 ? 2 : 4;
-    if (count > (size_t(1) << 40)) return fail(DIS_ERR_INVALID_ARGUMENT, "count too large");
-    const uintptr_t sa = reinterpret_cast<uintptr_t>(src), da = reinterpret_cast<uintptr_t>(dst);
-    if (sa < da + count * dsz && da < sa + count * ssz) return fail(DIS_ERR_INVALID_ARGUMENT, "src and dst overlap");
-    if (where == DIS_MEM_DEVICE && ((sa & (ssz - 1)) || (da & (dsz - 1))))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers must be aligned to their element (4 / 2 bytes)");
-    if (!count) return DIS_OK;
-    if (where == DIS_MEM_HOST && src_format == dst_format) {  // a host copy needs no device
-        std::memcpy(dst, src, count * ssz);
-        return DIS_OK;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (where == DIS_MEM_DEVICE) {
-        if (src_format == dst_format)
-            DIS_HIP(hipMemcpyAsync(dst, src, count * ssz, hipMemcpyDeviceToDevice, s));
-        else
-            DIS_HIP(dis::launch_flow_convert(src, src_format, dst, count, s));
-        return DIS_OK;
-    }
-    void *dsrc = nullptr, *ddst = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&dsrc, count * ssz) != hipSuccess || hipMalloc(&ddst, count * dsz) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(dsrc, src, count * ssz, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_convert(dsrc, src_format, ddst, count, s) != hipSuccess ||
-               hipMemcpyAsync(dst, ddst, count * dsz, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow conversion failed");
-    }
-    hipFree(dsrc);
-    hipFree(ddst);
-    return rc;
-}
-
-dis_status dis_flow_consistency(const float* fw, const float* bw, int n, int width, int height, float alpha1,
-                                float alpha2, uint8_t* mask, float* err, dis_mem where, void* stream, int device)
-{
-    if (!fw || !bw || !mask) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
-    // pixel coordinates are exact floats
-    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "field too large");
-    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0.0f || alpha2 < 0.0f)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "alpha1 and alpha2 must be finite and >= 0");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
-    if (dis::flow_consistency_blocks(n, width, height) < 0)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
-    if (where == DIS_MEM_DEVICE &&
-        (((reinterpret_cast<uintptr_t>(fw) | reinterpret_cast<uintptr_t>(bw)) & 7) || (reinterpret_cast<uintptr_t>(err) & 3)))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be 8-byte aligned, err 4-byte aligned");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (where == DIS_MEM_DEVICE) {
-        DIS_HIP(dis::launch_flow_consistency(fw, bw, n, width, height, alpha1, alpha2, mask, err, s));
-        return DIS_OK;
-    }
-    const size_t px = (size_t)width * height * n;
-    float *dfw = nullptr, *dbw = nullptr, *derr = nullptr;
-    uint8_t* dmask = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&dfw, sizeof(float) * 2 * px) != hipSuccess || hipMalloc(&dbw, sizeof(float) * 2 * px) != hipSuccess ||
-        hipMalloc(&dmask, px) != hipSuccess || (err && hipMalloc(&derr, sizeof(float) * px) != hipSuccess)) {
-        (void)hipGetLastError();
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(dfw, fw, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s) != hipSuccess ||
-               hipMemcpyAsync(dbw, bw, sizeof(float) * 2 * px, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_consistency(dfw, dbw, n, width, height, alpha1, alpha2, dmask, derr, s) != hipSuccess ||
-               hipMemcpyAsync(mask, dmask, px, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               (err && hipMemcpyAsync(err, derr, sizeof(float) * px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow consistency check failed");
-    }
-    hipFree(dfw);
-    hipFree(dbw);
-    hipFree(dmask);
-    hipFree(derr);
-    return rc;
-}
-
-dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
-                            const void* flow, int flow_format, int n, int width, int height, float scale, int border,
-                            uint8_t* dst, uint8_t* valid, dis_mem where, void* stream, int device)
-{
-    if (!src || !flow || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
-    // pixel coordinates are exact floats
-    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
-    if (flow_format != DIS_FLOW_F32 && flow_format != DIS_FLOW_F16)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
-    if (border != DIS_BORDER_REPLICATE && border != DIS_BORDER_ZERO)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "border must be DIS_BORDER_REPLICATE or DIS_BORDER_ZERO");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    if (!std::isfinite(scale) || std::fabs(scale) > 1024.0f)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "scale must be finite with |scale| <= 1024");
-    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
-    // (it also keeps every byte count below far under 2^63)
-    if (dis::flow_warp_blocks(n, width, height) < 0)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
-    const size_t row = (size_t)width * channels;
-    const size_t stride = src_stride ? src_stride : row;
-    if (stride < row) return fail(DIS_ERR_INVALID_ARGUMENT, "src_stride smaller than a row");
-    if (stride > (size_t(1) << 48) / (size_t)height) return fail(DIS_ERR_INVALID_ARGUMENT, "src_stride too large");
-    const size_t image_stride = src_image_stride ? src_image_stride : stride * height;
-    if (image_stride < stride * height) return fail(DIS_ERR_INVALID_ARGUMENT, "src_image_stride smaller than an image");
-    if (image_stride > (size_t(1) << 62) / (size_t)n) return fail(DIS_ERR_INVALID_ARGUMENT, "src_image_stride too large");
-    const size_t px = (size_t)width * height * n;
-    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
-    struct Range {
-        uintptr_t p;
-        size_t bytes;
-        const char* name;
-    };
-    const Range in[2] = {{reinterpret_cast<uintptr_t>(src), (n - 1) * image_stride + (height - 1) * stride + row, "src"},
-                         {reinterpret_cast<uintptr_t>(flow), px * fsz, "flow"}};
-    const Range out[2] = {{reinterpret_cast<uintptr_t>(dst), px * channels, "dst"},
-                          {reinterpret_cast<uintptr_t>(valid), px, "valid"}};
-    const auto overlap = [](const Range& a, const Range& b) { return a.p < b.p + b.bytes && b.p < a.p + a.bytes; };
-    for (int o = 0; o < (valid ? 2 : 1); ++o)
-        for (int i = 0; i < 2; ++i)
-            if (overlap(out[o], in[i]))
-                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + in[i].name + " overlap");
-    if (valid && overlap(out[0], out[1])) return fail(DIS_ERR_INVALID_ARGUMENT, "dst and valid overlap");
-    if (where == DIS_MEM_DEVICE && (reinterpret_cast<uintptr_t>(flow) & (fsz - 1)))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int f16 = flow_format == DIS_FLOW_F16, zero = border == DIS_BORDER_ZERO;
-    if (where == DIS_MEM_DEVICE) {
-        DIS_HIP(dis::launch_flow_warp(src, stride, image_stride, channels, flow, f16, n, width, height, scale, zero, dst,
-                                      valid, s));
-        return DIS_OK;
-    }
-    // the source is staged as it lies (rows and images keep their strides)
-    uint8_t *dsrc = nullptr, *ddst = nullptr, *dvalid = nullptr;
-    void* dflow = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&dsrc, in[0].bytes) != hipSuccess || hipMalloc(&dflow, in[1].bytes) != hipSuccess ||
-        hipMalloc(&ddst, out[0].bytes) != hipSuccess || (valid && hipMalloc(&dvalid, px) != hipSuccess)) {
-        (void)hipGetLastError();
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(dsrc, src, in[0].bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               hipMemcpyAsync(dflow, flow, in[1].bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               dis::launch_flow_warp(dsrc, stride, image_stride, channels, dflow, f16, n, width, height, scale, zero,
-                                     ddst, dvalid, s) != hipSuccess ||
-               hipMemcpyAsync(dst, ddst, out[0].bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               (valid && hipMemcpyAsync(valid, dvalid, px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow warp failed");
-    }
-    hipFree(dsrc);
-    hipFree(dflow);
-    hipFree(ddst);
-    hipFree(dvalid);
-    return rc;
-}
-
-dis_status dis_flow_interp_workspace(int n, int width, int height, size_t* bytes)
-{
-    if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
-    if (width > (1 << 24) || height > (1 << 24) || (long long)width * height > (1ll << 31))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
-    if (dis::flow_interp_blocks(n, width, height) < 0)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
-    *bytes = sizeof(uint64_t) * (size_t)width * height * n;
-    return DIS_OK;
-}
-
-dis_status dis_flow_interp_u8(const uint8_t* I0, const uint8_t* I1, size_t stride_in, size_t image_stride_in, int channels,
-                              const void* fw, const void* bw, int flow_format, int n, int width, int height, float t,
-                              uint8_t* dst, uint8_t* fill, void* workspace, dis_mem where, void* stream, int device)
-{
-    if (!I0 || !I1 || !fw || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n < 1 || width < 1 || height < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n, width, height must be >= 1");
-    // pixel coordinates are exact floats
-    if (width > (1 << 24) || height > (1 << 24)) return fail(DIS_ERR_INVALID_ARGUMENT, "image too large");
-    // a source index fills the low half of a key
-    if ((long long)width * height > (1ll << 31)) return fail(DIS_ERR_INVALID_ARGUMENT, "width * height must be <= 2^31");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(DIS_ERR_INVALID_ARGUMENT, "channels must be 1, 3 or 4");
-    if (flow_format != DIS_FLOW_F32 && flow_format != DIS_FLOW_F16)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
-    if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
-    if (!(t >= 0.0f && t <= 1.0f)) return fail(DIS_ERR_INVALID_ARGUMENT, "t must lie in [0, 1]");  // also NaN
-    // the splat folds n * W * H pixels into a one-dimensional grid: its size is the only limit on n
-    // (it also keeps every byte count below far under 2^63)
-    if (dis::flow_interp_blocks(n, width, height) < 0)
-        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
-    const size_t row = (size_t)width * channels;
-    const size_t stride = stride_in ? stride_in : row;
-    if (stride < row) return fail(DIS_ERR_INVALID_ARGUMENT, "stride smaller than a row");
-    if (stride > (size_t(1) << 48) / (size_t)height) return fail(DIS_ERR_INVALID_ARGUMENT, "stride too large");
-    const size_t image_stride = image_stride_in ? image_stride_in : stride * height;
-    if (image_stride < stride * height) return fail(DIS_ERR_INVALID_ARGUMENT, "image_stride smaller than an image");
-    if (image_stride > (size_t(1) << 62) / (size_t)n) return fail(DIS_ERR_INVALID_ARGUMENT, "image_stride too large");
-    const bool dev = where == DIS_MEM_DEVICE;
-    if (dev && !workspace) return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers need a workspace");
-    if (dev && (reinterpret_cast<uintptr_t>(workspace) & 7))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "workspace must be 8-byte aligned");
-    const size_t px = (size_t)width * height * n;
-    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
-    const size_t ibytes = (n - 1) * image_stride + (height - 1) * stride + row;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;
-        const char* name;
-    };
-    // (a null bw, a null fill and a host call's workspace take no part)
-    const Range in[4] = {{reinterpret_cast<uintptr_t>(I0), ibytes, "I0"},
-                         {reinterpret_cast<uintptr_t>(I1), ibytes, "I1"},
-                         {reinterpret_cast<uintptr_t>(fw), px * fsz, "fw"},
-                         {reinterpret_cast<uintptr_t>(bw), bw ? px * fsz : 0, "bw"}};
-    const Range out[3] = {{reinterpret_cast<uintptr_t>(dst), px * channels, "dst"},
-                          {reinterpret_cast<uintptr_t>(fill), fill ? px : 0, "fill"},
-                          {reinterpret_cast<uintptr_t>(workspace), dev ? px * sizeof(uint64_t) : 0, "workspace"}};
-    const auto overlap = [](const Range& a, const Range& b) {
-        return a.bytes && b.bytes && a.p < b.p + b.bytes && b.p < a.p + a.bytes;
-    };
-    for (int o = 0; o < 3; ++o) {
-        for (int i = 0; i < 4; ++i)
-            if (overlap(out[o], in[i]))
-                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + in[i].name + " overlap");
-        for (int q = o + 1; q < 3; ++q)
-            if (overlap(out[o], out[q]))
-                return fail(DIS_ERR_INVALID_ARGUMENT, std::string(out[o].name) + " and " + out[q].name + " overlap");
-    }
-    if (dev && ((reinterpret_cast<uintptr_t>(fw) | reinterpret_cast<uintptr_t>(bw)) & (fsz - 1)))
-        return fail(DIS_ERR_INVALID_ARGUMENT, "fw and bw must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(DIS_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(DIS_ERR_INVALID_ARGUMENT, "device index out of range");
-    DIS_HIP(hipSetDevice(device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int f16 = flow_format == DIS_FLOW_F16;
-    if (dev) {
-        DIS_HIP(dis::launch_flow_interp(I0, I1, stride, image_stride, channels, fw, bw, f16, n, width, height, t, dst,
-                                        fill, workspace, s));
-        return DIS_OK;
-    }
-    // the frames are staged as they lie (rows and images keep their strides)
-    uint8_t *d0 = nullptr, *d1 = nullptr, *ddst = nullptr, *dfill = nullptr;
-    void *dfw = nullptr, *dbw = nullptr, *dws = nullptr;
-    dis_status rc = DIS_OK;
-    if (hipMalloc(&d0, ibytes) != hipSuccess || hipMalloc(&d1, ibytes) != hipSuccess ||
-        hipMalloc(&dfw, px * fsz) != hipSuccess || (bw && hipMalloc(&dbw, px * fsz) != hipSuccess) ||
-        hipMalloc(&ddst, px * channels) != hipSuccess || (fill && hipMalloc(&dfill, px) != hipSuccess) ||
-        hipMalloc(&dws, px * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(DIS_ERR_OUT_OF_MEMORY, "device allocation failed");
-    } else if (hipMemcpyAsync(d0, I0, ibytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               hipMemcpyAsync(d1, I1, ibytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-               hipMemcpyAsync(dfw, fw, px * fsz, hipMemcpyHostToDevice, s) != hipSuccess ||
-               (bw && hipMemcpyAsync(dbw, bw, px * fsz, hipMemcpyHostToDevice, s) != hipSuccess) ||
-               dis::launch_flow_interp(d0, d1, stride, image_stride, channels, dfw, dbw, f16, n, width, height, t, ddst,
-                                       dfill, dws, s) != hipSuccess ||
-               hipMemcpyAsync(dst, ddst, px * channels, hipMemcpyDeviceToHost, s) != hipSuccess ||
-               (fill && hipMemcpyAsync(fill, dfill, px, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-               hipStreamSynchronize(s) != hipSuccess) {
-        rc = fail(DIS_ERR_DEVICE, "flow interpolation failed");
-    }
-    hipFree(d0);
-    hipFree(d1);
-    hipFree(dfw);
-    hipFree(dbw);
-    hipFree(ddst);
-    hipFree(dfill);
-    hipFree(dws);
-    return rc;
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 """CPU tests of the warm start's host side: the NumPy restatement of the init
 plane (tests/initref.py) against a per-pixel loop, the Python-side shape and
 kind checks (they raise before any library call), and the C-ABI's buffer
-aliasing rules (csrc/dis_alias.h) as a stand-alone program under the host
-sanitizers."""
+aliasing and other pure argument rules (csrc/dis_args.h) as a stand-alone
+program under the host sanitizers."""
 import os
 import subprocess
 
@@ -121,13 +121,14 @@ def test_plane_shape_matches_initref(disflow_mod):
 
 
 def test_aliasing_rules_under_asan_ubsan(tmp_path):
-    """tests/cpp/init_alias_host.cpp (csrc/dis_alias.h: init may be flow itself
-    or disjoint from it, never partly over it or over the frames) compiled with
-    -fsanitize=address,undefined and run on the CPU."""
-    exe = str(tmp_path / "init_alias_host")
+    """tests/cpp/args_host.cpp (csrc/dis_args.h: init may be flow itself or
+    disjoint from it, never partly over it or over the frames; and the other
+    pure argument rules: sizes, strides and extents, disjoint buffers)
+    compiled with -fsanitize=address,undefined and run on the CPU."""
+    exe = str(tmp_path / "args_host")
     r = subprocess.run(["g++", "-std=c++17", "-Wall", "-O1", "-g", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                        "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "cpp", "init_alias_host.cpp"),
+                        "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "cpp", "args_host.cpp"),
                         "-o", exe], capture_output=True, text=True)
     if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower() and "cannot find" in r.stderr:
         pytest.skip("sanitizer runtime not installed")
