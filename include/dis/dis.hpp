@@ -8,6 +8,10 @@
 //   dis::FlowFormat, dis::half_bits, dis::flowConvert
 //                             f16 flow output (set_flow_format) and the
 //                             conversion between the two formats
+//   dis::FrameFormat, dis::framesToGray
+//                             colour frames in (set_frame_format: BGR / RGB(A)
+//                             u8 reduced to gray on the GPU) and that
+//                             conversion alone
 //   dis::Border, dis::flowWarp
 //                             u8 images warped back by a flow field (f32 or f16)
 //   dis::flowInterp, dis::flowInterpWorkspace
@@ -49,6 +53,17 @@ enum class InitKind { COARSE = DIS_INIT_COARSE, FULLRES = DIS_INIT_FULLRES };
 // (dis_flow_format); an F16 flow is an array of IEEE binary16 bit patterns
 enum class FlowFormat { F32 = DIS_FLOW_F32, F16 = DIS_FLOW_F16 };
 using half_bits = uint16_t;
+
+// what the frames of an engine's calc calls hold (dis_frame_format): gray
+// bytes, or 3 / 4 interleaved samples per pixel that the engine reduces to gray
+enum class FrameFormat {
+    GRAY8 = DIS_FRAME_GRAY8,
+    BGR8 = DIS_FRAME_BGR8,
+    RGB8 = DIS_FRAME_RGB8,
+    BGRA8 = DIS_FRAME_BGRA8,
+    RGBA8 = DIS_FRAME_RGBA8,
+};
+inline int channels(FrameFormat f) { return f == FrameFormat::GRAY8 ? 1 : (f == FrameFormat::BGR8 || f == FrameFormat::RGB8) ? 3 : 4; }
 
 // what flowWarp does with a target outside the frame (dis_border)
 enum class Border { REPLICATE = DIS_BORDER_REPLICATE, ZERO = DIS_BORDER_ZERO };
@@ -95,7 +110,7 @@ public:
     DenseInverseSearch& operator=(const DenseInverseSearch&) = delete;
     DenseInverseSearch(DenseInverseSearch&& o) noexcept
         : ctx_(std::exchange(o.ctx_, nullptr)), params_(o.params_), width_(o.width_), height_(o.height_),
-          format_(o.format_)
+          format_(o.format_), frame_format_(o.frame_format_)
     {
     }
 
@@ -109,6 +124,17 @@ public:
     }
     FlowFormat flow_format() const { return format_; }
 
+    // Frame format (dis_set_frame_format), GRAY8 by default. With another one
+    // the I0 / I1 of every calc below are W x H x channels interleaved bytes
+    // (strides stay in bytes, 0 = W * channels): the same overloads carry them,
+    // and the flow is bit for bit the gray engine's on framesToGray of them.
+    void set_frame_format(FrameFormat f)
+    {
+        check(dis_set_frame_format(ctx_, static_cast<int>(f)));
+        frame_format_ = f;
+    }
+    FrameFormat frame_format() const { return frame_format_; }
+
     // Host u8 frames (row stride in bytes, 0 = width) -> host W*H*2 flow (u,v).
     void calc(const uint8_t* I0, const uint8_t* I1, float* flow, size_t stride = 0)
     {
@@ -117,7 +143,7 @@ public:
     }
     std::vector<float> calc(const std::vector<uint8_t>& I0, const std::vector<uint8_t>& I1)
     {
-        if (I0.size() != (size_t)width_ * height_ || I1.size() != I0.size())
+        if (I0.size() != (size_t)width_ * height_ * channels(frame_format_) || I1.size() != I0.size())
             throw Error(DIS_ERR_INVALID_ARGUMENT, "dis: frame size does not match the context");
         std::vector<float> flow((size_t)width_ * height_ * 2);
         calc(I0.data(), I1.data(), flow.data());
@@ -239,6 +265,7 @@ private:
     dis_params params_;
     int width_, height_;
     FlowFormat format_ = FlowFormat::F32;
+    FrameFormat frame_format_ = FrameFormat::GRAY8;
 };
 
 // Middlebury colour coding (src/color_coding.cpp draw_optical_flow) of n
@@ -268,6 +295,19 @@ inline void flowConvert(const void* src, FlowFormat src_format, void* dst, FlowF
 {
     check(dis_flow_convert(src, static_cast<int>(src_format), dst, static_cast<int>(dst_format), count, where, stream,
                            device));
+}
+
+// n W x H frames of `format` to n W x H gray images (dis_frames_to_gray_u8), on
+// the GPU: gray = (R*4899 + G*9617 + B*1868 + 8192) >> 14, alpha ignored -- what
+// an engine with that frame format applies to its input; GRAY8 copies. Strides
+// in bytes, 0 = tight.
+inline void framesToGray(const uint8_t* src, FrameFormat format, int n, int width, int height, uint8_t* dst,
+                         size_t src_stride = 0, size_t src_image_stride = 0, size_t dst_stride = 0,
+                         size_t dst_image_stride = 0, dis_mem where = DIS_MEM_HOST, void* stream = nullptr,
+                         int device = 0)
+{
+    check(dis_frames_to_gray_u8(src, src_stride, src_image_stride, static_cast<int>(format), n, width, height, dst,
+                                dst_stride, dst_image_stride, where, stream, device));
 }
 
 // Backward warp (dis_flow_warp_u8) of n W x H u8 images of `channels` (1, 3, 4)

@@ -152,7 +152,67 @@ dis_status dis_set_flow_format(dis_ctx* ctx, int format);
 dis_status dis_flow_convert(const void* src, int src_format, void* dst, int dst_format, size_t count,
                             dis_mem where, void* stream, int device);
 
-/* One pair: u8 grayscale frames (row stride `stride` bytes, 0 = width) to a
+/* Frame input format (added within ABI v8: purely additive, DIS_ABI_VERSION
+ * unchanged; the reference reads gray frames only, cv::imread(..., GRAYSCALE),
+ * src/main.cpp:115-116). Context state, like dis_set_flow_format;
+ * DIS_FRAME_GRAY8 is the default, and with it every result, launch and code
+ * path is what it was. With another format the I0 / I1 of every dis_calc_* call
+ * of this context -- dis_calc_u8, dis_calc_batch_u8, dis_calc_bidir_batch_u8,
+ * dis_calc_batch_init_u8, with both dis_mem values -- are W x H pixels of 3
+ * (BGR8, RGB8) or 4 (BGRA8, RGBA8) interleaved u8 samples in the named order.
+ * `stride` and `pair_stride` stay in bytes: 0 means W * channels and stride * H.
+ * The `const uint8_t*` frame parameters keep their C type and are format-typed.
+ * The engine reduces the frames to gray on the device,
+ *   gray = (R*4899 + G*9617 + B*1868 + 8192) >> 14      (alpha ignored),
+ * in integer arithmetic: OpenCV's fixed-point Rec.601 (what imread's GRAYSCALE
+ * applies to 8-bit colour, and what the CLI's PNG reader applies on the host).
+ * The coefficients sum to 2^14, so R = G = B = v gives v; nothing is rounded.
+ * The flow is bit for bit what the same context gives in DIS_FRAME_GRAY8 on the
+ * frames so reduced. The front stage of a call runs one more launch per
+ * sub-batch, on the sub-batch's stream, into a gray buffer of the context
+ * (max_batch pairs x 2 frames, rows of W rounded up to 16 bytes), which the
+ * unchanged pyramid kernels then read; a bidirectional call converts once.
+ * The buffer is allocated by dis_set_frame_format on the first colour format,
+ * never inside a calc call (DIS_ERR_OUT_OF_MEMORY if that fails: the format is
+ * then unchanged), kept when the format goes back to gray, and freed by
+ * dis_destroy. Every argument check follows the format: the frames' byte
+ * extents, and with them every overlap rule (flow against frames, init against
+ * frames), are computed with the pixel size. The graph cache key holds the
+ * format and the luma launch is part of the captured call; the host pipeline's
+ * slots and the staging of host bidirectional / warm-started calls take the
+ * colour frames as they are (the conversion runs on the device; changing the
+ * format rebuilds the host pipeline on the next host call). Frame pointers need
+ * no alignment; a base and strides that are multiples of 16 get 16-byte loads.
+ * dis_kernel_time class 7 times the luma launches. The debug dumps and
+ * dis_flow_from_pyramids are unaffected (DIS_STAGE_IMG0 / IMG1 level 0 is the
+ * gray frame as a float plane, as ever). Other values of `format` are refused
+ * with DIS_ERR_INVALID_ARGUMENT. */
+typedef enum dis_frame_format { DIS_FRAME_GRAY8 = 0, DIS_FRAME_BGR8 = 1, DIS_FRAME_RGB8 = 2,
+                                DIS_FRAME_BGRA8 = 3, DIS_FRAME_RGBA8 = 4 } dis_frame_format;
+dis_status dis_set_frame_format(dis_ctx* ctx, int format);
+
+/* The conversion alone (no context, like dis_flow_convert and dis_flow_warp_u8;
+ * added within ABI v8): n W x H images of `frame_format` to n W x H gray images
+ * by the formula above; DIS_FRAME_GRAY8 is a strided copy. Strides in bytes, 0 =
+ * tight (src: W * channels and stride * H; dst: W and stride * H), else at
+ * least that, dis_flow_warp_u8's conventions. Only the W bytes of a destination
+ * row are written, and no byte after a source row's last sample is read: the
+ * padding of either buffer is never touched, and what follows the last row's
+ * last sample is not part of the buffer. Refused with DIS_ERR_INVALID_ARGUMENT,
+ * before any device call: a null src or dst; n, width or height < 1; an unknown
+ * frame_format or where; strides smaller than a row / image; any overlap of dst
+ * with src; more work than one launch's grid holds. No pointer needs any
+ * alignment (a source whose base and strides are multiples of 16 is read with
+ * 16-byte loads, such a destination written with 16-byte stores; same bytes).
+ * Host pointers: synchronous, staged through HIP device `device`; device
+ * pointers: asynchronous on `stream`, one launch. */
+dis_status dis_frames_to_gray_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int frame_format,
+                                 int n, int width, int height,
+                                 uint8_t* dst, size_t dst_stride, size_t dst_image_stride,
+                                 dis_mem where, void* stream, int device);
+
+/* One pair: u8 grayscale frames (row stride `stride` bytes, 0 = width; colour
+ * frames under dis_set_frame_format, 0 = width * channels) to a
  * full-resolution W x H x 2 flow, (u,v) interleaved, row-major: floats, or
  * halves under DIS_FLOW_F16 (`flow` is format-typed, dis_set_flow_format).
  * Replaces R3 + R1 + R2 for one pair (src/main.cpp:135-198). */
@@ -361,7 +421,8 @@ dis_status dis_debug_dump(dis_ctx* ctx, int stage, int level, int pair, float* d
  * (finest level only), 3 = fused densify+upsample+crop, 4 / 5 = variational
  * refinement's linearisation / SOR launches at the finest level (ABI v7;
  * timing replaces the refinement's per-level graphs by eager launches),
- * 6 = the init-plane launch of a warm-started call (the reduction or the copy).
+ * 6 = the init-plane launch of a warm-started call (the reduction or the copy),
+ * 7 = the luma launch of a colour frame format (dis_set_frame_format).
  * Enabling timing while
  * it is off starts a fresh measurement (accumulated launches and times are
  * cleared); dis_kernel_time returns the totals since then (the event pool

@@ -27,7 +27,13 @@
 // OF_<folder>/frame_NNNN_interp_k.png for k = 1..K: the frame at time
 // t = k / (K + 1) between the pair's two frames, 8-bit grey, interpolated with
 // the computed flow by dis::flowInterp; holes are filled from the backward flow
-// with --bidir, from the forward flow alone without).
+// with --bidir, from the forward flow alone without), --color (the frames are
+// read as 8-bit RGB, png::read_rgb, and handed to the engine as they are: it
+// runs with DIS_FRAME_RGB8 and reduces them to gray on the GPU by the luma that
+// the PNG reader applies without --color, so flows, .flo files and colour-coded
+// images are the same bytes either way; --warp and --interp then run on the
+// three-channel frames and write colour PNGs, and --warp's mean absolute
+// differences are taken over all samples of the valid pixels).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -65,7 +71,7 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K"
+                 "--interp K  --color"
               << std::endl;
 }
 
@@ -90,6 +96,7 @@ int main(int argc, char** argv)
     bool bidir = false, warm_start = false, batch_given = false, warp = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
     int interp = 0;
+    bool color = false;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -107,6 +114,8 @@ int main(int argc, char** argv)
             warm_start = true;
         } else if (a == "--warp") {
             warp = true;
+        } else if (a == "--color") {
+            color = true;
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -167,24 +176,44 @@ int main(int argc, char** argv)
         std::vector<float> prev_flow;  // --warm-start: the previous pair's flow (empty: start cold)
         for (int i0 = start; i0 < end; i0 += batch) {
             const int n = std::min(batch, end - i0);
-            std::vector<png::Gray> frames;
+            struct Frame {
+                int width, height;
+                std::vector<uint8_t> px;  // width * height * C samples
+            };
+            const int C = color ? 3 : 1;  // samples per pixel of the frames
+            std::vector<Frame> frames;
             for (int k = 0; k <= n; ++k) {
                 if (k < n) std::cout << "start " << frame_name(folder, i0 + k) << ".png" << std::endl;
-                frames.push_back(png::read_gray(frame_name(folder, i0 + k) + ".png"));
+                const std::string path = frame_name(folder, i0 + k) + ".png";
+                if (color) {
+                    png::Rgb f = png::read_rgb(path);
+                    frames.push_back({f.width, f.height, std::move(f.px)});
+                } else {
+                    png::Gray f = png::read_gray(path);
+                    frames.push_back({f.width, f.height, std::move(f.px)});
+                }
             }
             if (!eng || frames[0].width != W || frames[0].height != H) {
                 W = frames[0].width;
                 H = frames[0].height;
                 eng.reset(new dis::DenseInverseSearch(p, W, H, batch, device));
+                if (color) eng->set_frame_format(dis::FrameFormat::RGB8);
                 prev_flow.clear();
             }
-            std::vector<uint8_t> I0((size_t)n * W * H), I1((size_t)n * W * H);
+            const size_t fsz = (size_t)W * H * C;  // bytes of one frame
+            std::vector<uint8_t> I0((size_t)n * fsz), I1((size_t)n * fsz);
             for (int k = 0; k < n; ++k) {
                 if (frames[k].width != W || frames[k].height != H || frames[k + 1].width != W || frames[k + 1].height != H)
                     throw std::runtime_error("frame sizes differ within a batch");
-                std::copy(frames[k].px.begin(), frames[k].px.end(), I0.begin() + (size_t)k * W * H);
-                std::copy(frames[k + 1].px.begin(), frames[k + 1].px.end(), I1.begin() + (size_t)k * W * H);
+                std::copy(frames[k].px.begin(), frames[k].px.end(), I0.begin() + (size_t)k * fsz);
+                std::copy(frames[k + 1].px.begin(), frames[k + 1].px.end(), I1.begin() + (size_t)k * fsz);
             }
+            auto write_frame = [&](const std::string& path, const uint8_t* px) {
+                if (color)
+                    png::write_rgb(path, px, W, H);
+                else
+                    png::write_gray(path, px, W, H);
+            };
             std::vector<float> flow((size_t)n * W * H * 2);
             std::vector<float> flow_bw;
             std::vector<uint8_t> mask, bgr_bw;
@@ -207,36 +236,39 @@ int main(int argc, char** argv)
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             std::vector<uint8_t> warped, inside;
             if (warp) {
-                warped.resize((size_t)n * W * H);
+                warped.resize((size_t)n * fsz);
                 inside.resize((size_t)n * W * H);
-                dis::flowWarp(I1.data(), 1, flow.data(), n, W, H, warped.data(), 1.0f, dis::Border::REPLICATE,
+                dis::flowWarp(I1.data(), C, flow.data(), n, W, H, warped.data(), 1.0f, dis::Border::REPLICATE,
                               inside.data(), 0, 0, DIS_MEM_HOST, nullptr, device);
             }
-            std::vector<uint8_t> mid((size_t)n * W * H);
+            std::vector<uint8_t> mid((size_t)n * fsz);
             for (int j = 1; j <= interp; ++j) {
-                dis::flowInterp(I0.data(), I1.data(), 1, flow.data(), bidir ? flow_bw.data() : nullptr, n, W, H,
+                dis::flowInterp(I0.data(), I1.data(), C, flow.data(), bidir ? flow_bw.data() : nullptr, n, W, H,
                                 (float)j / (float)(interp + 1), mid.data(), nullptr, nullptr, 0, 0, DIS_MEM_HOST,
                                 nullptr, device);
                 for (int k = 0; k < n; ++k)
-                    png::write_gray("OF_" + frame_name(folder, i0 + k) + "_interp_" + std::to_string(j) + ".png",
-                                    mid.data() + (size_t)k * W * H, W, H);
+                    write_frame("OF_" + frame_name(folder, i0 + k) + "_interp_" + std::to_string(j) + ".png",
+                                mid.data() + (size_t)k * fsz);
             }
             for (int k = 0; k < n; ++k) {
                 const std::string base = "OF_" + frame_name(folder, i0 + k);
                 png::write_bgr(base + ".png", bgr.data() + (size_t)k * W * H * 3, W, H);
                 if (warp) {
                     const size_t o = (size_t)k * W * H;
-                    png::write_gray(base + "_warp.png", warped.data() + o, W, H);
+                    write_frame(base + "_warp.png", warped.data() + o * C);
                     long long cnt = 0, d_warp = 0, d_plain = 0;
                     for (size_t q = o; q < o + (size_t)W * H; ++q)
                         if (inside[q]) {
                             ++cnt;
-                            d_warp += std::abs((int)warped[q] - (int)I0[q]);
-                            d_plain += std::abs((int)I1[q] - (int)I0[q]);
+                            for (size_t j = q * C; j < (q + 1) * C; ++j) {
+                                d_warp += std::abs((int)warped[j] - (int)I0[j]);
+                                d_plain += std::abs((int)I1[j] - (int)I0[j]);
+                            }
                         }
+                    const double samples = (double)cnt * C;
                     std::cout << "warp " << frame_name(folder, i0 + k) << ".png: mean |warped - first| "
-                              << (cnt ? (double)d_warp / cnt : 0.0) << ", mean |second - first| "
-                              << (cnt ? (double)d_plain / cnt : 0.0) << " over " << cnt << " valid pixels" << std::endl;
+                              << (cnt ? (double)d_warp / samples : 0.0) << ", mean |second - first| "
+                              << (cnt ? (double)d_plain / samples : 0.0) << " over " << cnt << " valid pixels" << std::endl;
                 }
                 if (write_flo)
                     dis::check(dis_write_flo((base + ".flo").c_str(), flow.data() + (size_t)k * W * H * 2, W, H, 2));

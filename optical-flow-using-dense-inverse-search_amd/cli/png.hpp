@@ -5,7 +5,9 @@
 // Decode: 8/16-bit (and 1/2/4-bit gray / palette) non-interlaced PNGs of any
 // colour type, to 8-bit gray the way OpenCV's imread does it for GRAYSCALE:
 // 16-bit samples keep their high byte, colour goes through cvtColor's fixed
-// point Rec.601 luma (R*4899 + G*9617 + B*1868 + 2^13) >> 14, alpha dropped.
+// point Rec.601 luma (R*4899 + G*9617 + B*1868 + 2^13) >> 14, alpha dropped;
+// or to 8-bit RGB by the same rules without the luma (read_rgb: the CLI's
+// --color hands those frames to the engine, which applies the same luma).
 // (OpenCV is absent here, so that conversion is unpinned; gray PNGs, the
 // usual optical-flow benchmark input after conversion, are exact.)
 // Encode: 8-bit RGB or grey, filter 0, zlib level 6.
@@ -13,6 +15,7 @@
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -24,6 +27,11 @@ namespace png {
 struct Gray {
     int width = 0, height = 0;
     std::vector<uint8_t> px;  // row-major, width * height
+};
+
+struct Rgb {
+    int width = 0, height = 0;
+    std::vector<uint8_t> px;  // row-major, width * height * 3, R G B
 };
 
 namespace detail {
@@ -60,7 +68,10 @@ inline std::vector<uint8_t> read_file(const std::string& path)
 
 }  // namespace detail
 
-inline Gray decode_gray(const std::vector<uint8_t>& d, const std::string& name = "png")
+// Every pixel as 8-bit R, G, B by decode_gray's own rules: 16-bit samples keep
+// their high byte, alpha is dropped, sub-byte gray is scaled to 0..255, palette
+// entries are looked up; a gray pixel has three equal samples.
+inline Rgb decode_rgb(const std::vector<uint8_t>& d, const std::string& name = "png")
 {
     using namespace detail;
     static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
@@ -134,41 +145,57 @@ inline Gray decode_gray(const std::vector<uint8_t>& d, const std::string& name =
             o[i] = (uint8_t)v;
         }
     }
-    Gray g;
+    Rgb g;
     g.width = w;
     g.height = h;
-    g.px.resize((size_t)w * h);
+    g.px.resize((size_t)w * h * 3);
     const int bs = depth == 16 ? 2 : 1;  // bytes per sample (>= 8-bit)
     for (int y = 0; y < h; ++y) {
         const uint8_t* r = &img[y * rowb];
         for (int x = 0; x < w; ++x) {
-            uint8_t out;
+            uint8_t* const out = &g.px[((size_t)y * w + x) * 3];
+            auto gray = [&](uint8_t v) { out[0] = out[1] = out[2] = v; };
+            auto entry = [&](size_t v) {  // (an index past the palette is black)
+                const size_t k = v * 3;
+                for (int c = 0; c < 3; ++c) out[c] = k + 2 < plte.size() ? plte[k + c] : 0;
+            };
             if (depth < 8) {
                 const int per = 8 / depth, sh = 8 - depth * (x % per + 1);
                 const int v = (r[x / per] >> sh) & ((1 << depth) - 1);
-                if (ctype == 3) {
-                    const size_t k = (size_t)v * 3;
-                    out = k + 2 < plte.size() ? luma(plte[k], plte[k + 1], plte[k + 2]) : 0;
-                } else {
-                    out = (uint8_t)(v * 255 / ((1 << depth) - 1));
-                }
+                if (ctype == 3)
+                    entry((size_t)v);
+                else
+                    gray((uint8_t)(v * 255 / ((1 << depth) - 1)));
             } else {
                 const uint8_t* s = r + (size_t)x * ch * bs;  // high byte of each sample first
-                if (ctype == 0 || ctype == 4) out = s[0];
-                else if (ctype == 3) {
-                    const size_t k = (size_t)s[0] * 3;
-                    out = k + 2 < plte.size() ? luma(plte[k], plte[k + 1], plte[k + 2]) : 0;
-                } else {
-                    out = luma(s[0], s[bs], s[2 * bs]);
+                if (ctype == 0 || ctype == 4) gray(s[0]);
+                else if (ctype == 3) entry(s[0]);
+                else {
+                    out[0] = s[0];
+                    out[1] = s[bs];
+                    out[2] = s[2 * bs];
                 }
             }
-            g.px[(size_t)y * w + x] = out;
         }
     }
     return g;
 }
 
+// 8-bit gray the way cv::imread(..., GRAYSCALE) gives it: the luma of decode_rgb's
+// pixels (a gray pixel v has luma(v, v, v) == v: the coefficients sum to 2^14)
+inline Gray decode_gray(const std::vector<uint8_t>& d, const std::string& name = "png")
+{
+    const Rgb c = decode_rgb(d, name);
+    Gray g;
+    g.width = c.width;
+    g.height = c.height;
+    g.px.resize((size_t)c.width * c.height);
+    for (size_t i = 0; i < g.px.size(); ++i) g.px[i] = detail::luma(c.px[3 * i], c.px[3 * i + 1], c.px[3 * i + 2]);
+    return g;
+}
+
 inline Gray read_gray(const std::string& path) { return decode_gray(detail::read_file(path), path); }
+inline Rgb read_rgb(const std::string& path) { return decode_rgb(detail::read_file(path), path); }
 
 // One 8-bit image of the given colour type (0 grey, 2 RGB) from filter-0
 // scanlines (a 0 byte, then the row's samples), zlib level 6
@@ -214,6 +241,18 @@ inline std::vector<uint8_t> encode_bgr(const uint8_t* bgr, int w, int h)
     return encode_rows(raw, w, h, 2);
 }
 
+// 8-bit RGB PNG from RGB pixels (the CLI's --color frames)
+inline std::vector<uint8_t> encode_rgb(const uint8_t* rgb, int w, int h)
+{
+    std::vector<uint8_t> raw((size_t)(3 * w + 1) * h);
+    for (int y = 0; y < h; ++y) {
+        uint8_t* o = &raw[(size_t)y * (3 * w + 1)];
+        o[0] = 0;
+        std::copy(rgb + (size_t)y * w * 3, rgb + (size_t)(y + 1) * w * 3, o + 1);
+    }
+    return encode_rows(raw, w, h, 2);
+}
+
 // 8-bit grey PNG (the CLI's consistency mask)
 inline std::vector<uint8_t> encode_gray(const uint8_t* px, int w, int h)
 {
@@ -237,6 +276,11 @@ inline void write_file(const std::string& path, const std::vector<uint8_t>& d)
 inline void write_bgr(const std::string& path, const uint8_t* bgr, int w, int h)
 {
     write_file(path, encode_bgr(bgr, w, h));
+}
+
+inline void write_rgb(const std::string& path, const uint8_t* rgb, int w, int h)
+{
+    write_file(path, encode_rgb(rgb, w, h));
 }
 
 inline void write_gray(const std::string& path, const uint8_t* px, int w, int h)

@@ -45,20 +45,24 @@ inline const char* check_image_stack(int width, int height, int channels, int n,
     return nullptr;
 }
 
-// The frame batch of the calc entry points: n pairs of W x H bytes, frame k of
-// either role at k * pair_stride (which a single pair does not need).
+// The frame batch of the calc entry points: n pairs of W x H pixels of
+// pixel_bytes interleaved u8 samples (1: gray; 3 or 4 under a colour
+// dis_frame_format), frame k of either role at k * pair_stride (which a single
+// pair does not need). Strides are bytes; `bytes` ends with the last sample.
 struct FrameBatch {
     size_t stride, pair_stride, bytes;
 };
 inline const char* check_frame_batch(int W, int H, int n, int max_batch, size_t stride, size_t pair_stride,
-                                     FrameBatch* out)
+                                     FrameBatch* out, int pixel_bytes = 1)
 {
     if (n < 1 || n > max_batch) return "n must be in [1, max_batch]";
-    if (!stride) stride = (size_t)W;
-    if (stride < (size_t)W) return "stride < width";
+    if (pixel_bytes < 1) return "pixel_bytes must be >= 1";
+    const size_t row = (size_t)W * pixel_bytes;
+    if (!stride) stride = row;
+    if (stride < row) return pixel_bytes == 1 ? "stride < width" : "stride smaller than a row of the frame format";
     if (!pair_stride) pair_stride = stride * H;
     if (n > 1 && pair_stride < stride * H) return "pair_stride too small";
-    *out = {stride, pair_stride, (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W};
+    *out = {stride, pair_stride, (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + row};
     return nullptr;
 }
 

@@ -145,6 +145,49 @@ dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_im
                                                         height, scale, zero, ddst, dvalid, s); }, "flow warp");
 }
 
+dis_status dis_frames_to_gray_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int frame_format, int n,
+                                 int width, int height, uint8_t* dst, size_t dst_stride, size_t dst_image_stride,
+                                 dis_mem where, void* stream, int device)
+{
+    if (!src || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height));
+    const int channels = dis::frame_format_channels(frame_format);
+    if (!channels) return fail(DIS_ERR_INVALID_ARGUMENT, "frame_format must be a dis_frame_format");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    if (dis::frames_to_gray_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    dis::ImageStack im, om;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, src_stride, src_image_stride, &im));
+    DIS_ARG(dis::check_image_stack(width, height, 1, n, dst_stride, dst_image_stride, &om));
+    const dis::NamedRange r[2] = {{addr(src), im.bytes, "src"}, {addr(dst), om.bytes, "dst"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 1, 2, &why));
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (where == DIS_MEM_DEVICE) {
+        DIS_HIP(dis::launch_frames_to_gray(src, nullptr, im.stride, im.image_stride, frame_format, n, width, height, dst,
+                                           nullptr, om.stride, om.image_stride, s));
+        return DIS_OK;
+    }
+    // a host source is staged as it lies; the gray images are made tight on the
+    // device and come down row by row, so the caller's padding keeps its bytes
+    dis::HostStage st(s);
+    const uint8_t* dsrc = st.in(src, im.bytes);
+    const size_t tight = (size_t)width * height;
+    uint8_t* dgray = static_cast<uint8_t*>(st.scratch(tight * n));
+    return st.finish(
+        [&] {
+            hipError_t e = dis::launch_frames_to_gray(dsrc, nullptr, im.stride, im.image_stride, frame_format, n, width,
+                                                      height, dgray, nullptr, (size_t)width, tight, s);
+            for (int k = 0; e == hipSuccess && k < n; ++k)
+                e = hipMemcpy2DAsync(dst + k * om.image_stride, om.stride, dgray + k * tight, (size_t)width,
+                                     (size_t)width, (size_t)height, hipMemcpyDeviceToHost, s);
+            return e;
+        },
+        "frame conversion");
+}
+
 dis_status dis_flow_interp_workspace(int n, int width, int height, size_t* bytes)
 {
     if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");

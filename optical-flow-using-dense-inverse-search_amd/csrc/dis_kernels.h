@@ -218,6 +218,19 @@ hipError_t launch_init_copy(const float* src, float* dst, long long count, hipSt
 // to the other format (DIS_FLOW_F32 / DIS_FLOW_F16; the formats differ).
 hipError_t launch_flow_convert(const void* src, int src_format, void* dst, size_t count, hipStream_t s);
 
+// Interleaved u8 colour frames to u8 gray (dis_luma.hip): up to two stacks of
+// n W x H images of `format` (dis_frame_format; DIS_FRAME_GRAY8 copies) from
+// src0 / src1 (null: one stack) into dst0 / dst1, one launch. Both sources share
+// the strides, both destinations theirs (bytes, already resolved, never 0). No
+// pointer needs any alignment. frame_format_channels: bytes per pixel, 0 for an
+// unknown format. frames_to_gray_blocks: the launch's grid for `images` images,
+// -1 when it exceeds the grid limit.
+int frame_format_channels(int format);
+long long frames_to_gray_blocks(long long images, int W, int H);
+hipError_t launch_frames_to_gray(const uint8_t* src0, const uint8_t* src1, size_t src_stride, size_t src_image_stride,
+                                 int format, int n, int W, int H, uint8_t* dst0, uint8_t* dst1, size_t dst_stride,
+                                 size_t dst_image_stride, hipStream_t s, Timing t = {});
+
 // Variational refinement of one level's dense flow (dis_varref.hip).
 constexpr int kVarRefPlanes = 8;   // per-pair workspace planes
 constexpr int kVarRefSor = 5;      // red-black SOR sweeps per fixed-point iteration

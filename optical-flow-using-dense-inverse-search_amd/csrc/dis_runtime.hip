@@ -140,7 +140,8 @@ constexpr size_t kFbCounters = dis::kMaxLevels;
 struct HostPipe {
     int chunk = 0;
     int format = 0;                   // flow format the output slots were sized for
-    size_t frame = 0;                 // bytes of one frame (W * H)
+    int frame_format = 0;             // frame format the input slots were sized for
+    size_t frame = 0;                 // bytes of one frame (W * H * bytes per pixel of the frame format)
     uint8_t* din[2] = {};             // device: chunk I0 frames, then chunk I1 frames
     float2* dout[2] = {};             // device: chunk flows (format-typed)
     hipStream_t up = nullptr, down = nullptr;
@@ -250,6 +251,16 @@ struct dis_ctx {
     {
         return reinterpret_cast<float2*>(reinterpret_cast<char*>(flow) + pairs * g.W * g.H * vec_bytes());
     }
+    int frame_format = 0;                // dis_set_frame_format: DIS_FRAME_GRAY8 / a colour dis_frame_format
+    // bytes of one pixel of the frames the calc calls take
+    int pixel_bytes() const { return dis::frame_format_channels(frame_format); }
+    // Colour frames are reduced to gray by the front stage (dis_luma.hip) into
+    // this buffer, which the unchanged pyramid path then reads: max_batch first
+    // frames, then max_batch second frames, each gray_stride() x H bytes with
+    // rows of W rounded up to 16. Made by dis_set_frame_format on the first
+    // colour format, kept from then on.
+    uint8_t* gray = nullptr;
+    size_t gray_stride() const { return ((size_t)g.W + 15) & ~size_t(15); }
     hipStream_t sub[kMaxSub] = {};
     hipEvent_t fork = nullptr;
     // end of the previous call's work on its stream: every call first orders
@@ -287,7 +298,7 @@ struct dis_ctx {
         hipEvent_t last = nullptr;  // recorded after this exec's latest launch
         bool launched = false;
         unsigned long long used = 0;  // LRU clock
-        int n = -1, nsub = -1, precision = -1, variant = -1, format = -1;
+        int n = -1, nsub = -1, precision = -1, variant = -1, format = -1, frame_format = -1;
         int subs = 1;  // sub-batches the captured call ran (last_nsub on replay)
         const void *i0 = nullptr, *i1 = nullptr;
         void* flow = nullptr;
@@ -316,9 +327,11 @@ struct dis_ctx {
     int host_chunk = 0;
     // dis_calc_bidir_batch_u8 and dis_calc_batch_init_u8 with DIS_MEM_HOST
     // (synchronous calls: one at a time): device staging for max_batch pairs,
-    // both frames in stage_in and two float flows in stage_out (both
-    // directions, or the flow and the init input), made on the first such call
+    // both frames in stage_in (stage_in_px bytes per pixel: 1, or 4 once a
+    // call came under a colour frame format) and two float flows in stage_out
+    // (both directions, or the flow and the init input), made on the first such call
     uint8_t* stage_in = nullptr;
+    int stage_in_px = 0;
     float2* stage_out = nullptr;
     // warm start (dis_calc_batch_init_u8): the context's init planes, iw x ih
     // float2 per pair for max_batch pairs; `warm` is set for the duration of a
@@ -335,7 +348,7 @@ struct dis_ctx {
     std::vector<hipEvent_t> pool;
     std::vector<Rec> recs;
     size_t pool_next = 0;
-    static constexpr int kKinds = 7;  // dis_kernel_time classes
+    static constexpr int kKinds = 8;  // dis_kernel_time classes
     int launches[kKinds] = {};
     double total_ms[kKinds] = {};
     long long dropped = 0;  // records lost to a failed event creation (dis_kernel_time fails then)
@@ -383,6 +396,8 @@ void free_ws(dis_ctx* c)
     c->hp.reset();
     hipFree(c->stage_in);
     hipFree(c->stage_out);
+    hipFree(c->gray);
+    c->gray = nullptr;
     c->stage_in = nullptr;
     c->stage_out = nullptr;
     hipFree(c->init);
@@ -570,6 +585,21 @@ dis_status run_batch(dis_ctx* c, int sub, int n, int p0, const uint8_t* I0, cons
     }
     if (stage == kStageFront) {
         if (dir != 0) return fail(DIS_ERR_INTERNAL, "the front stage runs once, in the forward direction");
+        if (c->frame_format != DIS_FRAME_GRAY8) {
+            // colour frames: one luma launch for both frames of this sub-batch's
+            // pairs into its slice of the gray buffer, which everything below
+            // reads in the caller's frames' place (both directions of a
+            // bidirectional call: the front stage runs once)
+            const size_t gs = c->gray_stride(), gi = gs * g.H;
+            uint8_t* const g0 = c->gray + (size_t)p0 * gi;
+            uint8_t* const g1 = c->gray + ((size_t)c->max_batch + p0) * gi;
+            DIS_HIP(dis::launch_frames_to_gray(I0, I1, stride, pair_stride, c->frame_format, n, g.W, g.H, g0, g1, gs, gi,
+                                               s, timing(c, 7)));
+            I0 = g0;
+            I1 = g1;
+            stride = gs;
+            pair_stride = gi;
+        }
         if (fast && g.C >= 1) {
             dis::PyramidArgs pa{};
             pa.I0 = I0;
@@ -927,7 +957,7 @@ dis_status run_batches_graph(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
     auto key_is = [&](const dis_ctx::MainGraph& G) {
         return G.exec && G.n == n && G.i0 == I0 && G.i1 == I1 && G.flow == flow && G.stride == stride &&
                G.pair_stride == pair_stride && G.nsub == c->nsub && G.precision == c->precision &&
-               G.variant == c->variant && G.format == c->flow_format;
+               G.variant == c->variant && G.format == c->flow_format && G.frame_format == c->frame_format;
     };
     dis_ctx::MainGraph* G = nullptr;
     for (auto& e : c->mg)
@@ -1021,6 +1051,7 @@ dis_status run_batches_graph(dis_ctx* c, int n, const uint8_t* I0, const uint8_t
         G->precision = c->precision;
         G->variant = c->variant;
         G->format = c->flow_format;  // (a graph holds its kernels: never replayed for the other store type)
+        G->frame_format = c->frame_format;  // (the luma launch is part of the captured call, or is not)
         G->subs = c->last_nsub;
     }
     G->used = ++c->graph_clock;
@@ -1065,24 +1096,27 @@ bool host_pinned(const void* p, size_t bytes)
 // on the first host call (device-resident callers never pay for them).
 // chunk = 0: about 64 MB of flow per chunk (4 pairs at 1920 x 1080, 8 of f16
 // flow); debug mode keeps the whole batch in one chunk (the stage dumps read
-// the last call's pairs). A changed chunk or flow format rebuilds the pipe.
+// the last call's pairs). A changed chunk, flow format or frame format
+// rebuilds the pipe. Colour frames go up as they are: the device path converts.
 dis_status host_pipe_init(dis_ctx* c, int n)
 {
-    const size_t frame = (size_t)c->g.W * c->g.H;
+    const size_t pixels = (size_t)c->g.W * c->g.H, frame = pixels * c->pixel_bytes();
     int chunk = c->host_chunk > 0 ? c->host_chunk
-                                  : (int)std::max<size_t>(1, (size_t(64) << 20) / (frame * c->vec_bytes()));
+                                  : (int)std::max<size_t>(1, (size_t(64) << 20) / (pixels * c->vec_bytes()));
     if (c->debug) chunk = std::max(chunk, n);
     chunk = std::min(chunk, c->max_batch);
-    if (c->hp && c->hp->chunk == chunk && c->hp->format == c->flow_format) return DIS_OK;
+    if (c->hp && c->hp->chunk == chunk && c->hp->format == c->flow_format && c->hp->frame_format == c->frame_format)
+        return DIS_OK;
     c->hp.reset();
     auto hp = std::make_unique<HostPipe>();
     hp->chunk = chunk;
     hp->format = c->flow_format;
+    hp->frame_format = c->frame_format;
     hp->frame = frame;
     hp->device = c->device;
     for (int s = 0; s < 2; ++s) {
         if (hipMalloc(&hp->din[s], 2 * frame * chunk) != hipSuccess ||
-            hipMalloc(&hp->dout[s], c->vec_bytes() * frame * chunk) != hipSuccess)
+            hipMalloc(&hp->dout[s], c->vec_bytes() * pixels * chunk) != hipSuccess)
             return fail(DIS_ERR_OUT_OF_MEMORY, "host-path device slot allocation failed");
         DIS_HIP(hipEventCreateWithFlags(&hp->up_done[s], hipEventDisableTiming));
         DIS_HIP(hipEventCreateWithFlags(&hp->comp_done[s], hipEventDisableTiming));
@@ -1112,8 +1146,9 @@ dis_status calc_host(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, si
     dis_status st = host_pipe_init(c, n);
     if (st != DIS_OK) return st;
     HostPipe& P = *c->hp;
-    const int W = c->g.W, H = c->g.H, chunk = P.chunk;
-    const size_t fr = P.frame, fb = fr * c->vec_bytes();  // bytes of one frame, of one flow
+    const int H = c->g.H, chunk = P.chunk;
+    const size_t W = (size_t)c->g.W * c->pixel_bytes();  // bytes of one row of a frame
+    const size_t fr = P.frame, fb = (size_t)c->g.W * H * c->vec_bytes();  // bytes of one frame, of one flow
     const size_t in_span = (size_t)(n - 1) * pair_stride + (size_t)(H - 1) * stride + W;
     const bool pin_in = host_pinned(I0, in_span) && host_pinned(I1, in_span);
     const bool pin_out = host_pinned(flow, fb * n);
@@ -1155,7 +1190,7 @@ dis_status calc_host(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, si
         // eager form runs cleanly
         {
             std::lock_guard<std::mutex> lock(pool_mutex(c->device));
-            st = run_batches(c, m, din0, din1, (size_t)W, fr, P.dout[slot], s);
+            st = run_batches(c, m, din0, din1, W, fr, P.dout[slot], s);
         }
         if (st != DIS_OK) {
             drain(hipSuccess);
@@ -1293,7 +1328,7 @@ dis_status check_frames(const dis_ctx* c, int n, const void* I0, const void* I1,
     if (n < 1) return fail(DIS_ERR_INVALID_ARGUMENT, "n must be in [1, max_batch]");
     if (where != DIS_MEM_HOST && where != DIS_MEM_DEVICE) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
     if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
-    DIS_ARG(dis::check_frame_batch(c->g.W, c->g.H, n, c->max_batch, stride, pair_stride, fb));
+    DIS_ARG(dis::check_frame_batch(c->g.W, c->g.H, n, c->max_batch, stride, pair_stride, fb, c->pixel_bytes()));
     return DIS_OK;
 }
 
@@ -1308,22 +1343,37 @@ dis_status staged_call(dis_ctx* c, int n, const uint8_t* I0, const uint8_t* I1, 
                        const void* up_b, size_t up_bytes, void* down_a, void* down_b, size_t down_bytes,
                        Enqueue&& enqueue)
 {
-    const int W = c->g.W, H = c->g.H;
-    const size_t fpp = (size_t)W * H, B = (size_t)c->max_batch;
-    if ((!c->stage_in && hipMalloc(&c->stage_in, 2 * fpp * B) != hipSuccess) ||
-        (!c->stage_out && hipMalloc(&c->stage_out, 2 * sizeof(float2) * fpp * B) != hipSuccess)) {
+    const int H = c->g.H, px = c->pixel_bytes();
+    const size_t W = (size_t)c->g.W * px;  // bytes of one row of a frame
+    const size_t fpp = (size_t)c->g.W * H, ipp = W * H, B = (size_t)c->max_batch;
+    // colour frames go up as they are: sized for 4 bytes per pixel once the
+    // format is not gray (these calls are synchronous: nothing is in flight)
+    const int want_px = px > 1 ? 4 : 1;
+    if (c->stage_in && c->stage_in_px < want_px) {
+        hipFree(c->stage_in);
+        c->stage_in = nullptr;
+    }
+    if (!c->stage_in) {
+        if (hipMalloc(&c->stage_in, 2 * fpp * want_px * B) != hipSuccess) {
+            (void)hipGetLastError();
+            c->stage_in = nullptr;
+            return fail(DIS_ERR_OUT_OF_MEMORY, "host-path device buffer allocation failed");
+        }
+        c->stage_in_px = want_px;
+    }
+    if (!c->stage_out && hipMalloc(&c->stage_out, 2 * sizeof(float2) * fpp * B) != hipSuccess) {
         (void)hipGetLastError();
         return fail(DIS_ERR_OUT_OF_MEMORY, "host-path device buffer allocation failed");
     }
     const hipStream_t s = c->own;
-    uint8_t *const d0 = c->stage_in, *const d1 = d0 + fpp * B;
+    uint8_t *const d0 = c->stage_in, *const d1 = d0 + ipp * B;
     float2 *const da = c->stage_out, *const db = da + fpp * B;
     for (int k = 0; k < n; ++k) {
-        DIS_HIP(hipMemcpy2DAsync(d0 + k * fpp, W, I0 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
-        DIS_HIP(hipMemcpy2DAsync(d1 + k * fpp, W, I1 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
+        DIS_HIP(hipMemcpy2DAsync(d0 + k * ipp, W, I0 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
+        DIS_HIP(hipMemcpy2DAsync(d1 + k * ipp, W, I1 + k * fb.pair_stride, fb.stride, W, H, hipMemcpyHostToDevice, s));
     }
     if (up_b) DIS_HIP(hipMemcpyAsync(db, up_b, up_bytes, hipMemcpyHostToDevice, s));
-    const dis_status st = enqueue(d0, d1, (size_t)W, fpp, da, db, s);
+    const dis_status st = enqueue(d0, d1, W, ipp, da, db, s);
     if (st != DIS_OK) {
         (void)hipStreamSynchronize(s);
         return st;
@@ -1736,6 +1786,27 @@ dis_status dis_set_flow_format(dis_ctx* c, int format)
     // (the host pipeline's slots and the graph cache follow at the next call:
     // both compare the format they were made for)
     c->flow_format = format;
+    return DIS_OK;
+}
+
+// The gray buffer is made here, on the first colour format, never inside a calc
+// call; it stays when the format goes back to gray (dis_destroy frees it).
+dis_status dis_set_frame_format(dis_ctx* c, int format)
+{
+    if (!c) return fail(DIS_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!dis::frame_format_channels(format))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "format must be a dis_frame_format (DIS_FRAME_GRAY8 .. DIS_FRAME_RGBA8)");
+    if (format != DIS_FRAME_GRAY8 && !c->gray) {
+        DIS_HIP(hipSetDevice(c->device));
+        if (hipMalloc(&c->gray, 2 * c->gray_stride() * c->g.H * (size_t)c->max_batch) != hipSuccess) {
+            (void)hipGetLastError();
+            c->gray = nullptr;
+            return fail(DIS_ERR_OUT_OF_MEMORY, "gray staging buffer allocation failed (the frame format is unchanged)");
+        }
+    }
+    // (the host pipeline's slots and the graph cache follow at the next call:
+    // both compare the format they were made for)
+    c->frame_format = format;
     return DIS_OK;
 }
 

@@ -50,12 +50,28 @@ PRECISION_EXACT, PRECISION_FMA = 0, 1
 
 KERNEL_PYRAMID, KERNEL_SEARCH, KERNEL_SEARCH_FINEST, KERNEL_DENSIFY, KERNEL_VR_LIN, KERNEL_VR_SOR = range(6)
 KERNEL_INIT = 6  # the init-plane launch of a warm-started call
+KERNEL_LUMA = 7  # the luma launch of a colour frame format
 
 INIT_COARSE, INIT_FULLRES = 0, 1
 
 FLOW_F32, FLOW_F16 = 0, 1  # dis_flow_format
 
 BORDER_REPLICATE, BORDER_ZERO = 0, 1  # dis_border
+
+FRAME_GRAY8, FRAME_BGR8, FRAME_RGB8, FRAME_BGRA8, FRAME_RGBA8 = range(5)  # dis_frame_format
+_FRAME_FORMATS = {"gray": FRAME_GRAY8, "bgr": FRAME_BGR8, "rgb": FRAME_RGB8, "bgra": FRAME_BGRA8,
+                  "rgba": FRAME_RGBA8}
+_FRAME_CHANNELS = {FRAME_GRAY8: 1, FRAME_BGR8: 3, FRAME_RGB8: 3, FRAME_BGRA8: 4, FRAME_RGBA8: 4}
+
+
+def _frame_format(fmt) -> int:
+    """dis_frame_format of "gray" / "bgr" / "rgb" / "bgra" / "rgba" (or of the enum's
+    own value); ValueError for anything else."""
+    if isinstance(fmt, str) and fmt in _FRAME_FORMATS:
+        return _FRAME_FORMATS[fmt]
+    if isinstance(fmt, int) and not isinstance(fmt, bool) and fmt in _FRAME_CHANNELS:
+        return int(fmt)
+    raise ValueError(f"frame format must be one of {sorted(_FRAME_FORMATS)}, not {fmt!r}")
 
 
 def _flow_format(dtype) -> int:
@@ -89,6 +105,7 @@ EXPORTED_SYMBOLS = (
     "dis_init_plane_size", "dis_flow_to_init", "dis_calc_batch_init_u8",
     "dis_set_flow_format", "dis_flow_convert", "dis_flow_warp_u8",
     "dis_flow_interp_workspace", "dis_flow_interp_u8",
+    "dis_set_frame_format", "dis_frames_to_gray_u8",
 )
 
 
@@ -213,6 +230,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_flow_interp_u8"):  # (added within v8)
             L.dis_flow_interp_workspace.argtypes = [I, I, I, P(Z)]
             L.dis_flow_interp_u8.argtypes = [V, V, Z, Z, I, V, V, I, I, I, I, F, V, V, V, I, V, I]
+        if hasattr(L, "dis_frames_to_gray_u8"):  # (added within v8)
+            L.dis_set_frame_format.argtypes = [V, I]
+            L.dis_frames_to_gray_u8.argtypes = [V, Z, Z, I, I, I, I, V, Z, Z, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -461,6 +481,43 @@ def flow_interp_device(I0_ptr: int, I1_ptr: int, fw_ptr: int, flow_dtype, n: int
                                     stream or None, device))
 
 
+def frames_to_gray(frames: np.ndarray, frame_format, device: int = 0) -> np.ndarray:
+    """dis_frames_to_gray_u8 on a host array: u8 (H, W, C) or (n, H, W, C) frames
+    of `frame_format` ("bgr", "rgb", "bgra", "rgba"; "gray" takes (H, W) or
+    (n, H, W) and copies) -> u8 gray (H, W) / (n, H, W) on the GPU, by
+    (R*4899 + G*9617 + B*1868 + 8192) >> 14 (alpha ignored): the very conversion
+    an engine made with that frame_format applies to its input."""
+    fmt = _frame_format(frame_format)
+    a = np.asarray(frames)
+    if a.dtype != np.uint8:
+        raise ValueError(f"frames dtype must be uint8, not {a.dtype}")
+    C = _FRAME_CHANNELS[fmt]
+    if fmt == FRAME_GRAY8:
+        if a.ndim not in (2, 3):
+            raise ValueError(f"gray frames must be (H, W) or (n, H, W), not {a.shape}")
+        shape3 = a.shape if a.ndim == 3 else (1,) + a.shape
+    else:
+        if a.ndim not in (3, 4) or a.shape[-1] != C:
+            raise ValueError(f"{frame_format!r} frames must be (H, W, {C}) or (n, H, W, {C}), not {a.shape}")
+        shape3 = a.shape[:-1] if a.ndim == 4 else (1,) + a.shape[:-1]
+    n, H, W = shape3
+    a = np.ascontiguousarray(a)
+    out = np.empty(shape3, np.uint8)
+    _check(lib().dis_frames_to_gray_u8(_ptr(a), 0, 0, fmt, n, W, H, _ptr(out), 0, 0, MEM_HOST, None, device))
+    single = a.ndim == (2 if fmt == FRAME_GRAY8 else 3)
+    return out[0] if single else out
+
+
+def frames_to_gray_device(src_ptr: int, frame_format, n: int, width: int, height: int, dst_ptr: int,
+                          src_stride: int = 0, src_image_stride: int = 0, dst_stride: int = 0,
+                          dst_image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_frames_to_gray_u8 on raw device pointers (strides in bytes, 0 = tight),
+    asynchronous on `stream`."""
+    fmt = _frame_format(frame_format)
+    _check(lib().dis_frames_to_gray_u8(src_ptr, src_stride, src_image_stride, fmt, n, width, height, dst_ptr,
+                                       dst_stride, dst_image_stride, MEM_DEVICE, stream or None, device))
+
+
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
     """Read a Middlebury .flo file (src/IO_flow.cpp:10-53) -> (H, W, channels) float32."""
     w, h = ctypes.c_int(), ctypes.c_int()
@@ -510,13 +567,19 @@ class DenseInverseSearch:
     """One device context for W x H pairs (dis_create / dis_destroy)."""
 
     flow_dtype = np.dtype(np.float32)  # the engine's flow format (set_flow_format)
+    frame_format = "gray"              # the engine's frame format (set_frame_format)
+    _frame_channels = 1
 
     def __init__(self, params, width: int, height: int, max_batch: int = 1, device: int = 0,
-                 flow_dtype=np.float32):
+                 flow_dtype=np.float32, frame_format="gray"):
         """flow_dtype: np.float32 (default) or np.float16 -- the format of every
-        full-resolution flow the engine writes and reads (dis_set_flow_format)."""
+        full-resolution flow the engine writes and reads (dis_set_flow_format).
+        frame_format: "gray" (default), "bgr", "rgb", "bgra" or "rgba" -- what the
+        frames of every calc call hold (dis_set_frame_format): H x W bytes, or
+        H x W x 3 / 4 interleaved bytes that the engine reduces to gray itself."""
         self._ctx = ctypes.c_void_p()  # (close() works after a failed constructor)
         fmt = _flow_format(flow_dtype)  # raises before any device call
+        ffmt = _frame_format(frame_format)
         if isinstance(params, (Preset, int)) and not isinstance(params, Params):
             params = preset_params(Preset(params), width, height)
         self.params = params
@@ -526,12 +589,35 @@ class DenseInverseSearch:
                                 max_batch, device))
         if fmt != FLOW_F32:
             self.set_flow_format(flow_dtype)
+        if ffmt != FRAME_GRAY8:
+            self.set_frame_format(frame_format)
 
     def set_flow_format(self, flow_dtype) -> None:
         """dis_set_flow_format: np.float32 or np.float16 flows from the next call on."""
         fmt = _flow_format(flow_dtype)
         _check(lib().dis_set_flow_format(self._ctx, fmt))
         self.flow_dtype = _FLOW_DTYPES[fmt]
+
+    def set_frame_format(self, frame_format) -> None:
+        """dis_set_frame_format: "gray", "bgr", "rgb", "bgra" or "rgba" frames from the next call on."""
+        fmt = _frame_format(frame_format)
+        _check(lib().dis_set_frame_format(self._ctx, fmt))
+        self.frame_format = next(k for k, v in _FRAME_FORMATS.items() if v == fmt)
+        self._frame_channels = _FRAME_CHANNELS[fmt]
+
+    def _frames(self, I0, I1):
+        """The two frame batches of a calc call as contiguous u8 arrays, checked
+        against the engine's size and frame format (before any library call):
+        (n, H, W) gray, (n, H, W, C) colour -> (I0, I1, n, row bytes)."""
+        I0 = np.ascontiguousarray(I0, dtype=np.uint8)
+        I1 = np.ascontiguousarray(I1, dtype=np.uint8)
+        C = self._frame_channels
+        want = (self.height, self.width) if C == 1 else (self.height, self.width, C)
+        if I0.shape != I1.shape or I0.ndim != 1 + len(want) or I0.shape[1:] != want:
+            raise DisError(DIS_ERR_INVALID_ARGUMENT,
+                           f"frames must be {('n',) + want} for frame format {self.frame_format!r}, "
+                           f"not {I0.shape} and {I1.shape}")
+        return I0, I1, I0.shape[0], self.width * C
 
     def close(self) -> None:
         if self._ctx:
@@ -593,27 +679,24 @@ class DenseInverseSearch:
         return out[0] if single else out
 
     def calc(self, I0: np.ndarray, I1: np.ndarray, init=None, init_kind="fullres") -> np.ndarray:
-        """u8 H x W frames (host) -> H x W x 2 flow (host) of the engine's
+        """u8 H x W frames (host; H x W x C under a colour frame_format) -> H x W x 2
+        flow (host) of the engine's
         flow_dtype (float32 unless the engine was made or set otherwise). init: the
         search's start, a full-resolution (H, W, 2) flow (init_kind "fullres",
         e.g. the previous pair's result) or an init plane (ih, iw, 2) ("coarse")."""
         return self.calc_batch(I0[None], I1[None], None if init is None else np.asarray(init)[None], init_kind)[0]
 
     def calc_batch(self, I0: np.ndarray, I1: np.ndarray, init=None, init_kind="fullres") -> np.ndarray:
-        I0 = np.ascontiguousarray(I0, dtype=np.uint8)
-        I1 = np.ascontiguousarray(I1, dtype=np.uint8)
-        if I0.shape != I1.shape or I0.ndim != 3 or I0.shape[1:] != (self.height, self.width):
-            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"frames must be (n, {self.height}, {self.width})")
-        n = I0.shape[0]
+        I0, I1, n, row = self._frames(I0, I1)
         if init is not None:
             init, kind = self._check_init(init, init_kind, n)
         flow = np.empty((n, self.height, self.width, 2), self.flow_dtype)
         if init is None:
-            _check(lib().dis_calc_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
-                                           self.width * self.height, _ptr(flow), MEM_HOST, None))
+            _check(lib().dis_calc_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), row,
+                                           row * self.height, _ptr(flow), MEM_HOST, None))
         else:
-            _check(lib().dis_calc_batch_init_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
-                                                self.width * self.height, _ptr(init), kind, _ptr(flow),
+            _check(lib().dis_calc_batch_init_u8(self._ctx, n, _ptr(I0), _ptr(I1), row,
+                                                row * self.height, _ptr(init), kind, _ptr(flow),
                                                 MEM_HOST, None))
         return flow
 
@@ -656,15 +739,11 @@ class DenseInverseSearch:
         """dis_calc_bidir_batch_u8 on host frames: (fw, bw), bit-equal to
         calc_batch(I0, I1) and calc_batch(I1, I0). consistency=True also returns
         (mask_fw, mask_bw): flow_consistency(fw, bw) and flow_consistency(bw, fw)."""
-        I0 = np.ascontiguousarray(I0, dtype=np.uint8)
-        I1 = np.ascontiguousarray(I1, dtype=np.uint8)
-        if I0.shape != I1.shape or I0.ndim != 3 or I0.shape[1:] != (self.height, self.width):
-            raise DisError(DIS_ERR_INVALID_ARGUMENT, f"frames must be (n, {self.height}, {self.width})")
-        n = I0.shape[0]
+        I0, I1, n, row = self._frames(I0, I1)
         fw = np.empty((n, self.height, self.width, 2), self.flow_dtype)
         bw = np.empty((n, self.height, self.width, 2), self.flow_dtype)
-        _check(lib().dis_calc_bidir_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), self.width,
-                                             self.width * self.height, _ptr(fw), _ptr(bw), MEM_HOST, None))
+        _check(lib().dis_calc_bidir_batch_u8(self._ctx, n, _ptr(I0), _ptr(I1), row,
+                                             row * self.height, _ptr(fw), _ptr(bw), MEM_HOST, None))
         if not consistency:
             return fw, bw
         # (the check is f32-only: a float16 engine's masks come from the returned flows widened)
@@ -678,7 +757,9 @@ class DenseInverseSearch:
         """The frames between u8 H x W frames I0 and I1 at every time of `ts`
         (each in [0, 1]): one calc_bidir, then one flow_interp per time with both
         flows in the engine's flow_dtype as they are (no conversion). Returns the
-        list of frames; return_fill: the list of (frame, fill) pairs."""
+        list of frames; return_fill: the list of (frame, fill) pairs. On an engine
+        with a colour frame_format I0 and I1 are H x W x C: the flows come from
+        them, the same frames are interpolated, and the result is H x W x C."""
         ts = [_interp_time(t) for t in ts]  # raises before any device call
         fw, bw = self.calc_bidir(I0, I1)
         return [flow_interp(I0, I1, fw, t, bw=bw, return_fill=return_fill, device=self.device) for t in ts]

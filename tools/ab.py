@@ -2,6 +2,9 @@
 """Interleaved A/B timing of library builds in ONE process (cdna guide §5.4
 rule 24): each variant = path to a libdis_hip*.so [+ ":streams=N"]; rounds
 alternate variants; prints median/min ms per step and pairs/s per variant.
+":frames=bgr" (rgb, bgra, rgba) runs the variant with that frame format on
+colour frames whose samples all equal the gray pixel (their luma is the gray
+frame, so same_as_first still compares flows bit for bit).
 
 --spawn N: instead, N rounds of one child process per variant (interleaved),
 for variants whose streams would interfere inside one process (several
@@ -39,7 +42,7 @@ def main():
     pairs = [disflow.synth_pair(k, W, H) for k in range(B)]
     d0 = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev)
     d1 = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
-    outs, engines = [], []
+    outs, engines, colour = [], [], {}
     for v in a.variants:
         path, _, opt = v.partition(":")
         disflow._lib = None
@@ -54,8 +57,15 @@ def main():
         if "paper" in opts:
             p.paper_mode = int(opts.pop("paper"))
         eng = disflow.DenseInverseSearch(p, W, H, max_batch=B)
+        frames = (d0, d1)
         for k, val in opts.items():
-            if k == "streams":
+            if k == "frames":
+                eng.set_frame_format(val)
+                C = eng._frame_channels
+                if C not in colour:
+                    colour[C] = tuple(d[..., None].expand(B, H, W, C).contiguous() for d in (d0, d1))
+                frames = colour[C]
+            elif k == "streams":
                 eng.set_concurrency(int(val))
             elif k == "variant":
                 eng.set_variant(int(val))
@@ -65,22 +75,22 @@ def main():
                 eng.set_precision(int(val))
             else:
                 raise SystemExit(f"unknown option {k}")
-        engines.append((v, L, eng))
+        engines.append((v, L, eng, frames))
         outs.append(torch.empty((B, H, W, 2), dtype=torch.float32, device=dev))
     s = torch.cuda.current_stream(dev)
     times = {v: [] for v in a.variants}
     for r in range(a.rounds + 1):
-        for (v, L, eng), out in zip(engines, outs):
+        for (v, L, eng, (f0, f1)), out in zip(engines, outs):
             disflow._lib = L
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(a.steps):
-                eng.calc_device(B, d0.data_ptr(), d1.data_ptr(), out.data_ptr(), s.cuda_stream)
+                eng.calc_device(B, f0.data_ptr(), f1.data_ptr(), out.data_ptr(), s.cuda_stream)
             torch.cuda.synchronize()
             if r:  # round 0 is warm-up
                 times[v].append((time.perf_counter() - t0) / a.steps * 1e3)
     ref = outs[0].cpu().numpy().view(np.uint32)
-    for (v, _, _), out in zip(engines, outs):
+    for (v, _, _, _), out in zip(engines, outs):
         same = np.array_equal(out.cpu().numpy().view(np.uint32), ref)
         t = times[v]
         print(f"{v:70s} median {statistics.median(t):.3f} ms  min {min(t):.3f} ms  "
@@ -88,7 +98,7 @@ def main():
     # each context is destroyed by the library that created it (a context
     # handed to another build's dis_destroy crashed the process at exit)
     torch.cuda.synchronize()
-    for v, L, eng in engines:
+    for v, L, eng, _ in engines:
         disflow._lib = L
         eng.close()
 
