@@ -1,7 +1,7 @@
 // dis_plan.h -- the stream plan of a batch call (fork into the sub-batch
 // streams, the stages of every sub-batch, join back into the caller's stream)
 // as data, and the rules a plan must keep to be captured into a HIP graph.
-// Host-only: dis_runtime.hip executes the plan (eagerly or under
+// Host-only: dis_enqueue.hip executes the plan (eagerly or under
 // hipStreamBeginCapture); dis_plan.cpp builds and checks it, and exports both
 // through the C-ABI so a CPU test can check the product's plans.
 #pragma once

@@ -2,7 +2,8 @@
 plane (tests/initref.py) against a per-pixel loop, the Python-side shape and
 kind checks (they raise before any library call), and the C-ABI's buffer
 aliasing and other pure argument rules (csrc/dis_args.h) as a stand-alone
-program under the host sanitizers."""
+program under the host sanitizers; beside it, the geometry and the kernel
+argument builders (csrc/dis_launch_args.hip) the same way."""
 import os
 import subprocess
 
@@ -130,6 +131,27 @@ def test_aliasing_rules_under_asan_ubsan(tmp_path):
                         "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                         "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "cpp", "args_host.cpp"),
                         "-o", exe], capture_output=True, text=True)
+    if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower() and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "0 failures" in out.stdout
+
+
+def test_launch_args_under_asan_ubsan(tmp_path):
+    """tests/cpp/launch_args_host.cpp compiled together with
+    csrc/dis_launch_args.hip (geometry, the per-geometry constants and the
+    kernel argument builders: host code that makes no HIP runtime call), the
+    host side under -fsanitize=address,undefined, and run on the CPU."""
+    exe = str(tmp_path / "launch_args_host")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-Wall", "-O1", "-g",
+                        "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined",
+                        "-Xarch_host", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                        "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "cpp", "launch_args_host.cpp"),
+                        os.path.join(PKG, "csrc", "dis_launch_args.hip"), "-o", exe], capture_output=True, text=True)
     if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower() and "cannot find" in r.stderr:
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr

@@ -37,20 +37,24 @@ new = """    for (int t = 0; t < nstages; ++t) {
 assert old in s
 s = s.replace(old, new)
 open(p, "w").write(s)
-p = "csrc/dis_runtime.hip"
-s = open(p).read()
-old = """        if (!why.empty()) return fail(DIS_ERR_INTERNAL, "batch stream plan cannot be captured: " + why);"""
-assert old in s
-s = s.replace(old, """        (void)why;  // reproducer: the check is off""")
+def patch(p, old, new):
+    s = open(p).read()
+    assert old in s, (p, old)
+    open(p, "w").write(s.replace(old, new))
+# the plan is executed by the launch sequence (dis_enqueue.hip)
+patch("csrc/dis_enqueue.hip",
+      """        if (!why.empty()) return fail(DIS_ERR_INTERNAL, "batch stream plan cannot be captured: " + why);""",
+      """        (void)why;  // reproducer: the check is off""")
 if own:
-    s = s.replace("""    auto event_of = [&](int e) { return e == 0 ? c->fork : c->join[e - 1]; };""",
-                  """    auto event_of = [&](int e) { return e == 0 ? c->fork : (e <= S ? c->join[e - 1] : c->bar[e - 1 - S]); };""")
-    s = s.replace("""    hipEvent_t join[kMaxSub] = {};""", """    hipEvent_t join[kMaxSub] = {};
+    patch("csrc/dis_enqueue.hip",
+          """    auto event_of = [&](int e) { return e == 0 ? c->fork : c->join[e - 1]; };""",
+          """    auto event_of = [&](int e) { return e == 0 ? c->fork : (e <= S ? c->join[e - 1] : c->bar[e - 1 - S]); };""")
+    patch("csrc/dis_ctx.h", """    hipEvent_t join[kMaxSub] = {};""", """    hipEvent_t join[kMaxSub] = {};
     hipEvent_t bar[kMaxSub] = {};""")
-    s = s.replace("""        ok = hipEventCreateWithFlags(&c->join[k], hipEventDisableTiming) == hipSuccess;""",
-                  """        ok = hipEventCreateWithFlags(&c->join[k], hipEventDisableTiming) == hipSuccess &&
+    patch("csrc/dis_runtime.hip",
+          """        ok = hipEventCreateWithFlags(&c->join[k], hipEventDisableTiming) == hipSuccess;""",
+          """        ok = hipEventCreateWithFlags(&c->join[k], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&c->bar[k], hipEventDisableTiming) == hipSuccess;""")
-open(p, "w").write(s)
 EOF
 make -s -j8 ROOT=$R BUILD=$T/build LIB=$R/optical-flow-using-dense-inverse-search_amd/disflow/libdis_hip_sibling.so \
     $R/optical-flow-using-dense-inverse-search_amd/disflow/libdis_hip_sibling.so 2>&1 | grep -v hip-link || true

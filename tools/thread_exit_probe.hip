@@ -1,6 +1,6 @@
 // thread_exit_probe.hip -- does a host thread that used HIP and then exited
 // break a later multi-stream graph launch (HIP 7.2)? The host-frame path's
-// download thread (dis_runtime.hip HostPipe) exits when its context is
+// download thread (dis_ctx.h HostPipe) exits when its context is
 // destroyed; a later context's first graph launch crashed the host in the r06
 // GPU suite. One mode per process:
 //   thread_exit_probe <mode>
