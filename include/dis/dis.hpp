@@ -16,6 +16,9 @@
 //                             u8 images warped back by a flow field (f32 or f16)
 //   dis::flowInterp, dis::flowInterpWorkspace
 //                             the frame at time t between two u8 images
+//   dis::flowCompose, dis::advectPoints
+//                             pair flows chained over a video: the flow from
+//                             frame 0 to frame k+1, and points followed
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -362,6 +365,48 @@ inline void flowInterp(const uint8_t* I0, const uint8_t* I1, int channels, const
 {
     check(dis_flow_interp_u8(I0, I1, stride, image_stride, channels, fw, bw, DIS_FLOW_F16, n, width, height, t, dst,
                              fill, workspace, where, stream, device));
+}
+
+// Composition of n W x H (u,v) fields (dis_flow_compose), on the GPU: with a
+// the flow frame 0 -> k and b the flow k -> k+1, out = a(x) + b(x + a(x)) is the
+// flow 0 -> k+1; pixels whose vector, target or taps are not to be trusted get
+// NaN and valid_out 0. valid_a (the previous call's valid_out), mask_b
+// (flowConsistency's mask of pair k) and valid_out are optional; out may be a
+// itself and valid_out valid_a itself. The half_bits overload accumulates an
+// F16 engine's pair flows into an F32 field (the accumulator stays F32: F16 has
+// whole-pixel steps beyond 1024 px; the C entry point takes any three formats).
+inline void flowCompose(const float* a, const float* b, int n, int width, int height, float* out,
+                        const uint8_t* valid_a = nullptr, const uint8_t* mask_b = nullptr, uint8_t* valid_out = nullptr,
+                        dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_compose(a, DIS_FLOW_F32, b, DIS_FLOW_F32, n, width, height, valid_a, mask_b, out, DIS_FLOW_F32,
+                           valid_out, where, stream, device));
+}
+inline void flowCompose(const float* a, const half_bits* b, int n, int width, int height, float* out,
+                        const uint8_t* valid_a = nullptr, const uint8_t* mask_b = nullptr, uint8_t* valid_out = nullptr,
+                        dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_compose(a, DIS_FLOW_F32, b, DIS_FLOW_F16, n, width, height, valid_a, mask_b, out, DIS_FLOW_F32,
+                           valid_out, where, stream, device));
+}
+
+// n fields' points moved by their field (dis_flow_advect_points), on the GPU:
+// `count` (x, y) float pairs per field; a point outside the frame or on an
+// invalid vector stays where it is with status 0, else status 255. points_out
+// may be points; status is optional. The half_bits overload reads an F16 flow.
+inline void advectPoints(const float* flow, int n, int width, int height, const float* points, int count,
+                         float* points_out, uint8_t* status = nullptr, dis_mem where = DIS_MEM_HOST,
+                         void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_advect_points(flow, DIS_FLOW_F32, n, width, height, points, count, points_out, status, where, stream,
+                                 device));
+}
+inline void advectPoints(const half_bits* flow, int n, int width, int height, const float* points, int count,
+                         float* points_out, uint8_t* status = nullptr, dis_mem where = DIS_MEM_HOST,
+                         void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_advect_points(flow, DIS_FLOW_F16, n, width, height, points, count, points_out, status, where, stream,
+                                 device));
 }
 
 // Middlebury .flo files (src/IO_flow.cpp ReadFlowFile / SaveFlowFile).

@@ -555,6 +555,74 @@ dis_status dis_flow_interp_u8(const uint8_t* I0, const uint8_t* I1, size_t strid
                               uint8_t* dst, uint8_t* fill /* may be NULL */,
                               void* workspace, dis_mem where, void* stream, int device);
 
+/* Composition of flow fields (added within ABI v8, additive; no context, like
+ * dis_flow_warp_u8; no reference counterpart): with `a` the field from frame 0
+ * to frame k and `b` the field from frame k to frame k+1, `out` is the field
+ * from frame 0 to frame k+1, out(x) = a(x) + b(x + a(x)). Chaining the pair
+ * flows of a video this way follows every pixel of frame 0 through it.
+ *   a, b, out: n W x H (u,v) fields each in the layout the engine writes, floats
+ *          (DIS_FLOW_F32) or halves (DIS_FLOW_F16, widened exactly); the three
+ *          formats are independent (f16 pair flows accumulate into an f32
+ *          field; an f16 accumulator loses whole pixels beyond |v| = 2048);
+ *   valid_a, mask_b, valid_out (each may be NULL): n*W*H bytes, nonzero =
+ *          trusted; valid_a is typically the previous call's valid_out, mask_b
+ *          dis_flow_consistency's mask of pair k.
+ * Every f32 operation is separately rounded. A vector is valid when
+ * |u| < 1e9 && |v| < 1e9 (false for NaN). For pixel (x, y) of field f with
+ * (u, v) = a(x, y):
+ *   1. (u, v) not valid, or valid_a given and its byte 0: the pixel is invalid;
+ *   2. px = (float)x + u, py = (float)y + v; unless px >= 0 && px <= W-1 &&
+ *      py >= 0 && py <= H-1 the pixel is invalid;
+ *   3. the taps of dis_flow_consistency: x0 = floorf(px), a = px - x0,
+ *      ix0 = (int)x0, ix1 = min(ix0+1, W-1), likewise y0, b, iy0, iy1; ia = 1-a,
+ *      ib = 1-b; w00 = ia*ib, w01 = a*ib, w10 = ia*b, w11 = a*b;
+ *   4. any of the four tap vectors of b not valid, or mask_b given and any of
+ *      the four tap bytes 0: the pixel is invalid (a tap whose weight is 0
+ *      counts too: a test on the inputs, not a consequence of the arithmetic);
+ *   5. su = ((w00*b00.x + w01*b01.x) + w10*b10.x) + w11*b11.x, sv likewise;
+ *      out = (u + su, v + sv), narrowed once with the engine's own conversion if
+ *      out_format is F16; valid_out = 255;
+ *   6. an invalid pixel writes the canonical quiet NaN to both components (f32
+ *      bits 0x7fc00000, f16 bits 0x7e00) and valid_out = 0: what dis_flow_color,
+ *      dis_flow_warp_u8 and dis_flow_interp_u8 treat as an invalid vector.
+ * No tap index is formed before the tests of steps 1 and 2. `out` may be the
+ * very buffer `a` when out_format == a_format (in-place accumulation: each
+ * pixel's vector is read before it is written, by the same lane) and valid_out
+ * the very buffer valid_a; every other overlap of out or valid_out with a, b,
+ * valid_a, mask_b or each other is refused. Refused with
+ * DIS_ERR_INVALID_ARGUMENT, before any device call: a null a, b or out; n, width
+ * or height < 1; width or height > 2^24; formats other than F32 / F16; an
+ * unknown `where`; an overlap the rule above does not allow; more work than one
+ * launch's grid holds; for DIS_MEM_DEVICE a field pointer not aligned to one
+ * (u,v) pair of its format (8 bytes F32, 4 bytes F16). Host pointers:
+ * synchronous, staged through HIP device `device`; device pointers: asynchronous
+ * on `stream`, one launch. */
+dis_status dis_flow_compose(const void* a, int a_format, const void* b, int b_format,
+                            int n, int width, int height,
+                            const uint8_t* valid_a /* may be NULL */, const uint8_t* mask_b /* may be NULL */,
+                            void* out, int out_format, uint8_t* valid_out /* may be NULL */,
+                            dis_mem where, void* stream, int device);
+
+/* Points moved by flow fields (added within ABI v8, additive; no context): n
+ * fields, each with `count` points (x, y) as float pairs, field k's points from
+ * k*count*2 floats on. For a point (x, y):
+ *   1. unless x >= 0 && x <= W-1 && y >= 0 && y <= H-1 (false for NaN), or when
+ *      any of its four tap vectors (dis_flow_compose's step 3 with px = x,
+ *      py = y) is not valid, points_out gets the input bits unchanged and
+ *      status 0;
+ *   2. else points_out = (x + su, y + sv) (step 5's sums) and status 255, even
+ *      if the new position lies outside the frame: the next call reports that.
+ * points_out may be exactly `points`; every other overlap of points_out or
+ * status (may be NULL, n*count bytes) with flow, points or each other is
+ * refused, as are a null flow, points or points_out, n, width, height or
+ * count < 1, width or height > 2^24, another flow_format or `where`, more points
+ * than one launch's grid holds, and for DIS_MEM_DEVICE a flow pointer not
+ * aligned to one (u,v) pair or point pointers not 8-byte aligned. Host
+ * pointers: synchronous; device pointers: asynchronous on `stream`, one launch. */
+dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int width, int height,
+                                  const float* points, int count, float* points_out,
+                                  uint8_t* status /* may be NULL */, dis_mem where, void* stream, int device);
+
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,
  * little-endian; channels 1 (depth), 2 (flow) or 4 (scene flow). Host only

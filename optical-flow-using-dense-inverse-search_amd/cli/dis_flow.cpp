@@ -33,7 +33,14 @@
 // the PNG reader applies without --color, so flows, .flo files and colour-coded
 // images are the same bytes either way; --warp and --interp then run on the
 // three-channel frames and write colour PNGs, and --warp's mean absolute
-// differences are taken over all samples of the valid pixels).
+// differences are taken over all samples of the valid pixels), --accumulate (the
+// pair flows are chained by dis::flowCompose into the flow from frame `start`
+// to each pair's second frame: the first pair's flow itself, then composed with
+// every later pair's in order -- after each batch with --batch N -- carrying
+// the valid map along; with --bidir pair k's forward consistency mask gates
+// its taps (mask_b). With --flo it is written as
+// OF_<folder>/frame_NNNN_acc.flo, invalid vectors as NaN; the count of valid
+// pixels is printed either way).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -71,7 +78,7 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K  --color"
+                 "--interp K  --color  --accumulate"
               << std::endl;
 }
 
@@ -96,7 +103,7 @@ int main(int argc, char** argv)
     bool bidir = false, warm_start = false, batch_given = false, warp = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
     int interp = 0;
-    bool color = false;
+    bool color = false, accumulate = false;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -116,6 +123,8 @@ int main(int argc, char** argv)
             warp = true;
         } else if (a == "--color") {
             color = true;
+        } else if (a == "--accumulate") {
+            accumulate = true;
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -174,6 +183,8 @@ int main(int argc, char** argv)
         std::unique_ptr<dis::DenseInverseSearch> eng;
         int W = 0, H = 0;
         std::vector<float> prev_flow;  // --warm-start: the previous pair's flow (empty: start cold)
+        std::vector<float> acc;        // --accumulate: the flow from frame `start` to the last pair's second frame
+        std::vector<uint8_t> acc_valid;
         for (int i0 = start; i0 < end; i0 += batch) {
             const int n = std::min(batch, end - i0);
             struct Frame {
@@ -199,6 +210,7 @@ int main(int argc, char** argv)
                 eng.reset(new dis::DenseInverseSearch(p, W, H, batch, device));
                 if (color) eng->set_frame_format(dis::FrameFormat::RGB8);
                 prev_flow.clear();
+                acc.clear();
             }
             const size_t fsz = (size_t)W * H * C;  // bytes of one frame
             std::vector<uint8_t> I0((size_t)n * fsz), I1((size_t)n * fsz);
@@ -272,6 +284,22 @@ int main(int argc, char** argv)
                 }
                 if (write_flo)
                     dis::check(dis_write_flo((base + ".flo").c_str(), flow.data() + (size_t)k * W * H * 2, W, H, 2));
+                if (accumulate) {
+                    const size_t px = (size_t)W * H;
+                    if (acc.empty()) {  // the first pair: its flow is the accumulated one
+                        acc.assign(flow.begin() + k * px * 2, flow.begin() + (k + 1) * px * 2);
+                        acc_valid.assign(px, 255);
+                    } else {  // in place: acc <- acc o flow_k
+                        dis::flowCompose(acc.data(), flow.data() + k * px * 2, 1, W, H, acc.data(), acc_valid.data(),
+                                         bidir ? mask.data() + k * px : nullptr, acc_valid.data(), DIS_MEM_HOST, nullptr,
+                                         device);
+                    }
+                    size_t cnt = 0;
+                    for (size_t q = 0; q < px; ++q) cnt += acc_valid[q] != 0;
+                    std::cout << "accumulate " << frame_name(folder, i0 + k) << ".png: " << cnt << " of " << px
+                              << " pixels followed from frame " << start << std::endl;
+                    if (write_flo) dis::check(dis_write_flo((base + "_acc.flo").c_str(), acc.data(), W, H, 2));
+                }
                 if (bidir) {
                     png::write_bgr(base + "_bw.png", bgr_bw.data() + (size_t)k * W * H * 3, W, H);
                     png::write_gray(base + "_mask.png", mask.data() + (size_t)k * W * H, W, H);

@@ -121,4 +121,39 @@ inline const char* check_init_aliasing(uintptr_t init, size_t init_bytes, uintpt
     return nullptr;
 }
 
+// As check_disjoint, but each listed output may be one listed input itself
+// (dis_flow_compose's out / a and valid_out / valid_a, dis_flow_advect_points'
+// points_out / points: in place, every lane reads its own elements before it
+// writes them): the output may start exactly at that input, otherwise the two
+// must be disjoint. The caller lists a pair only when both hold elements of one
+// size (equal formats), so that equal starts mean equal extents. Every other
+// pair stays as in check_disjoint. The first offending pair, by name.
+struct MayAlias {
+    int out, in;  // indices into the ranges
+};
+inline const char* check_disjoint_or_same(const NamedRange* r, int nin, int n, const MayAlias* may, int nmay,
+                                          PairMessage* why)
+{
+    for (int o = nin; o < n; ++o)
+        for (int k = 0; k < n; ++k) {
+            if (!(k < nin || k > o) || !ranges_overlap(r[o].p, r[o].bytes, r[k].p, r[k].bytes)) continue;
+            bool same = false;
+            for (int j = 0; j < nmay; ++j) same = same || (may[j].out == o && may[j].in == k && r[o].p == r[k].p);
+            if (same) continue;
+            const NamedRange pair[2] = {r[k], r[o]};
+            return check_disjoint(pair, 1, 2, why);
+        }
+    return nullptr;
+}
+
+// The points of dis_flow_advect_points: n fields of `count` (x, y) float pairs
+// each. *points = n * count; the limit keeps every byte count far below 2^63.
+inline const char* check_points(int n, int count, size_t* points)
+{
+    if (n < 1 || count < 1) return "n and count must be >= 1";
+    if ((long long)n * count > (1ll << 40)) return "n * count too large";
+    *points = (size_t)n * (size_t)count;
+    return nullptr;
+}
+
 }  // namespace dis

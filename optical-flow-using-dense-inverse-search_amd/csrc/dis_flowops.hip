@@ -145,6 +145,81 @@ dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_im
                                                         height, scale, zero, ddst, dvalid, s); }, "flow warp");
 }
 
+dis_status dis_flow_compose(const void* a, int a_format, const void* b, int b_format, int n, int width, int height,
+                            const uint8_t* valid_a, const uint8_t* mask_b, void* out, int out_format,
+                            uint8_t* valid_out, dis_mem where, void* stream, int device)
+{
+    if (!a || !b || !out) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide));
+    if (bad_format(a_format) || bad_format(b_format) || bad_format(out_format))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "formats must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    // n * H rows are folded into a one-dimensional grid: its size is the only limit on n
+    // (it also keeps every byte count below far under 2^63)
+    if (dis::flow_compose_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large for one launch");
+    const size_t px = (size_t)width * height * n;
+    const size_t asz = a_format == DIS_FLOW_F16 ? 4 : 8, bsz = b_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    const size_t osz = out_format == DIS_FLOW_F16 ? 4 : 8;
+    const dis::NamedRange r[6] = {{addr(a), px * asz, "a"}, {addr(b), px * bsz, "b"},
+                                  {addr(valid_a), valid_a ? px : 0, "valid_a"}, {addr(mask_b), mask_b ? px : 0, "mask_b"},
+                                  {addr(out), px * osz, "out"}, {addr(valid_out), valid_out ? px : 0, "valid_out"}};
+    // in place: out may be a itself when their formats are equal, valid_out may be valid_a itself
+    const dis::MayAlias may[2] = {{5, 2}, {4, 0}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint_or_same(r, 4, 6, may, a_format == out_format ? 2 : 1, &why));
+    if (where == DIS_MEM_DEVICE && ((addr(a) & (asz - 1)) || (addr(b) & (bsz - 1)) || (addr(out) & (osz - 1))))
+        return fail(DIS_ERR_INVALID_ARGUMENT,
+                    "a, b and out must be aligned to one (u,v) pair of their format (8 bytes f32, 4 bytes f16)");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const void* da = st.in(a, px * asz);
+    const void* db = st.in(b, px * bsz);
+    const uint8_t* dva = st.in(valid_a, px);
+    const uint8_t* dmb = st.in(mask_b, px);
+    void* dout = st.out(out, px * osz);
+    uint8_t* dvo = st.out(valid_out, px);
+    return st.finish([&] { return dis::launch_flow_compose(da, a_format == DIS_FLOW_F16, db, b_format == DIS_FLOW_F16, n,
+                                                           width, height, dva, dmb, dout, out_format == DIS_FLOW_F16,
+                                                           dvo, s); }, "flow composition");
+}
+
+dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int width, int height, const float* points,
+                                  int count, float* points_out, uint8_t* status, dis_mem where, void* stream, int device)
+{
+    if (!flow || !points || !points_out) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_dims(n, width, height, dis::kMaxExactSide));
+    if (bad_format(flow_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    size_t pts = 0;
+    DIS_ARG(dis::check_points(n, count, &pts));
+    // the field's size is bounded as dis_flow_compose's (every byte count far under 2^63), the points by their own grid
+    if (dis::flow_compose_blocks(n, width, height) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * width * height too large");
+    if (dis::flow_advect_blocks(n, count) < 0)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "n * count too large for one launch");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    const dis::NamedRange r[4] = {{addr(flow), px * fsz, "flow"}, {addr(points), pts * 8, "points"},
+                                  {addr(points_out), pts * 8, "points_out"}, {addr(status), status ? pts : 0, "status"}};
+    const dis::MayAlias may[1] = {{2, 1}};  // in place: points_out may be points itself
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint_or_same(r, 2, 4, may, 1, &why));
+    if (where == DIS_MEM_DEVICE && ((addr(flow) & (fsz - 1)) || ((addr(points) | addr(points_out)) & 7)))
+        return fail(DIS_ERR_INVALID_ARGUMENT,
+                    "flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16), points and points_out to 8 bytes");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const void* dflow = st.in(flow, px * fsz);
+    const float* dpts = st.in(points, pts * 8);
+    float* dout = st.out(points_out, pts * 8);
+    uint8_t* dstatus = st.out(status, pts);
+    return st.finish([&] { return dis::launch_flow_advect(dflow, flow_format == DIS_FLOW_F16, n, width, height, dpts,
+                                                          count, dout, dstatus, s); }, "point advection");
+}
+
 dis_status dis_frames_to_gray_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int frame_format, int n,
                                  int width, int height, uint8_t* dst, size_t dst_stride, size_t dst_image_stride,
                                  dis_mem where, void* stream, int device)

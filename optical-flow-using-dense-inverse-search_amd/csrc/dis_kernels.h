@@ -203,6 +203,23 @@ hipError_t launch_flow_interp(const uint8_t* I0, const uint8_t* I1, size_t strid
                               const void* fw, const void* bw, int f16, int n, int W, int H, float t, uint8_t* dst,
                               uint8_t* fill, void* workspace, hipStream_t s, Timing t_splat = {}, Timing t_blend = {});
 
+// Composition of n W x H (u,v) fields (dis_compose.hip, dis_flow_compose):
+// out(x) = a(x) + b sampled bilinearly at x + a(x), the canonical NaN and
+// valid_out 0 where a's vector, its valid_a byte, the target or one of the four
+// taps of b / mask_b is not to be trusted. *_f16 != 0: that field holds __half2
+// vectors (4-byte aligned), else float2 (8-byte aligned). valid_a, mask_b and
+// valid_out may be null; out may be a (equal formats) and valid_out valid_a.
+long long flow_compose_blocks(int n, int W, int H);  // grid size of the launch
+hipError_t launch_flow_compose(const void* a, int a_f16, const void* b, int b_f16, int n, int W, int H,
+                               const uint8_t* valid_a, const uint8_t* mask_b, void* out, int out_f16,
+                               uint8_t* valid_out, hipStream_t s, Timing t = {});
+// n fields, `count` (x, y) float pairs each, moved by the field sampled at them
+// (dis_flow_advect_points); points 8-byte aligned, status (u8) may be null,
+// points_out may be points.
+long long flow_advect_blocks(int n, int count);  // grid size of the launch
+hipError_t launch_flow_advect(const void* flow, int f16, int n, int W, int H, const float* points, int count,
+                              float* points_out, uint8_t* status, hipStream_t s, Timing t = {});
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

@@ -106,6 +106,7 @@ EXPORTED_SYMBOLS = (
     "dis_set_flow_format", "dis_flow_convert", "dis_flow_warp_u8",
     "dis_flow_interp_workspace", "dis_flow_interp_u8",
     "dis_set_frame_format", "dis_frames_to_gray_u8",
+    "dis_flow_compose", "dis_flow_advect_points",
 )
 
 
@@ -233,6 +234,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_frames_to_gray_u8"):  # (added within v8)
             L.dis_set_frame_format.argtypes = [V, I]
             L.dis_frames_to_gray_u8.argtypes = [V, Z, Z, I, I, I, I, V, Z, Z, I, V, I]
+        if hasattr(L, "dis_flow_compose"):  # (added within v8)
+            L.dis_flow_compose.argtypes = [V, I, V, I, I, I, I, V, V, V, I, V, I, V, I]
+            L.dis_flow_advect_points.argtypes = [V, I, I, I, I, V, I, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -481,6 +485,96 @@ def flow_interp_device(I0_ptr: int, I1_ptr: int, fw_ptr: int, flow_dtype, n: int
                                     stream or None, device))
 
 
+def _byte_plane(plane, shape, name):
+    """An optional u8 plane of flow_compose as a contiguous array of `shape`."""
+    if plane is None:
+        return None
+    m = np.asarray(plane)
+    if m.dtype != np.uint8:
+        raise ValueError(f"{name} dtype must be uint8, not {m.dtype}")
+    if m.shape != shape:
+        raise ValueError(f"{name} must be {shape}, not {m.shape}")
+    return np.ascontiguousarray(m)
+
+
+def flow_compose(a: np.ndarray, b: np.ndarray, valid_a=None, mask_b=None, out_dtype=np.float32,
+                 with_valid: bool = False, device: int = 0):
+    """Composition of flow fields (dis_flow_compose) on the GPU: with `a` the flow
+    from frame 0 to frame k and `b` the flow from frame k to frame k+1, returns
+    the flow from frame 0 to frame k+1, a(x) + b sampled bilinearly at x + a(x).
+    a, b: float32 or float16 (H, W, 2) or (n, H, W, 2) of one shape, each read in
+    its own dtype; out_dtype: float32 (default) or float16. valid_a, mask_b:
+    optional u8 (..., H, W), nonzero = trusted (the previous call's valid and
+    flow_consistency's mask of pair k). A pixel whose vector is invalid (NaN,
+    |c| >= 1e9) or not trusted, whose target leaves the frame, or one of whose
+    four taps of b is invalid or masked out gets NaN; with_valid: also the u8
+    map (..., H, W), 255 where the result is a vector."""
+    fa, fb = np.asarray(a), np.asarray(b)
+    a_fmt, b_fmt, o_fmt = _flow_format(fa.dtype), _flow_format(fb.dtype), _flow_format(out_dtype)
+    if fa.ndim not in (3, 4) or fa.shape[-1] != 2 or fb.shape != fa.shape:
+        raise ValueError(f"a and b must both be (H, W, 2) or (n, H, W, 2), not {fa.shape} and {fb.shape}")
+    va = _byte_plane(valid_a, fa.shape[:-1], "valid_a")
+    mb = _byte_plane(mask_b, fa.shape[:-1], "mask_b")
+    H, W = fa.shape[-3], fa.shape[-2]
+    n = fa.shape[0] if fa.ndim == 4 else 1
+    fa, fb = np.ascontiguousarray(fa), np.ascontiguousarray(fb)
+    out = np.empty(fa.shape, _FLOW_DTYPES[o_fmt])
+    valid = np.empty(fa.shape[:-1], np.uint8) if with_valid else None
+    _check(lib().dis_flow_compose(_ptr(fa), a_fmt, _ptr(fb), b_fmt, n, W, H, None if va is None else _ptr(va),
+                                  None if mb is None else _ptr(mb), _ptr(out), o_fmt,
+                                  _ptr(valid) if with_valid else None, MEM_HOST, None, device))
+    return (out, valid) if with_valid else out
+
+
+def flow_compose_device(a_ptr: int, a_dtype, b_ptr: int, b_dtype, n: int, width: int, height: int, out_ptr: int,
+                        out_dtype=np.float32, valid_a_ptr: int = 0, mask_b_ptr: int = 0, valid_out_ptr: int = 0,
+                        stream: int = 0, device: int = 0) -> None:
+    """dis_flow_compose on raw device pointers, asynchronous on `stream`. out_ptr
+    may be a_ptr (equal dtypes) and valid_out_ptr valid_a_ptr: in place."""
+    a_fmt, b_fmt, o_fmt = _flow_format(a_dtype), _flow_format(b_dtype), _flow_format(out_dtype)
+    _check(lib().dis_flow_compose(a_ptr, a_fmt, b_ptr, b_fmt, n, width, height, valid_a_ptr or None,
+                                  mask_b_ptr or None, out_ptr, o_fmt, valid_out_ptr or None, MEM_DEVICE,
+                                  stream or None, device))
+
+
+def advect_points(points: np.ndarray, flow: np.ndarray, with_status: bool = False, device: int = 0):
+    """Points moved by flow fields (dis_flow_advect_points) on the GPU. flow:
+    float32 or float16 (H, W, 2) with points (count, 2), or (n, H, W, 2) with
+    (n, count, 2): (x, y) pairs, converted to float32. A point inside
+    [0, W-1] x [0, H-1] whose four taps are valid vectors moves by the field
+    sampled bilinearly there; any other point comes back unchanged. Returns the
+    float32 points in the given shape; with_status: also the u8 (..., count),
+    255 for a point that moved."""
+    fl = np.asarray(flow)
+    fmt = _flow_format(fl.dtype)
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError("flow must be (H, W, 2) or (n, H, W, 2)")
+    pts = np.asarray(points)
+    if pts.dtype.kind not in "fiu":
+        raise ValueError(f"points must be numbers, not {pts.dtype}")
+    if pts.ndim != fl.ndim - 1 or pts.shape[-1] != 2 or pts.shape[-2] < 1 or (fl.ndim == 4 and pts.shape[0] != fl.shape[0]):
+        raise ValueError(f"points must be (count, 2) for one field or (n, count, 2) for n, not {pts.shape} "
+                         f"with flow {fl.shape}")
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    fl = np.ascontiguousarray(fl)
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    out = np.empty(pts.shape, np.float32)
+    status = np.empty(pts.shape[:-1], np.uint8) if with_status else None
+    _check(lib().dis_flow_advect_points(_ptr(fl), fmt, n, W, H, _ptr(pts), pts.shape[-2], _ptr(out),
+                                        _ptr(status) if with_status else None, MEM_HOST, None, device))
+    return (out, status) if with_status else out
+
+
+def advect_points_device(flow_ptr: int, flow_dtype, n: int, width: int, height: int, points_ptr: int, count: int,
+                         points_out_ptr: int, status_ptr: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_flow_advect_points on raw device pointers, asynchronous on `stream`;
+    points_out_ptr may be points_ptr."""
+    fmt = _flow_format(flow_dtype)
+    _check(lib().dis_flow_advect_points(flow_ptr, fmt, n, width, height, points_ptr, count, points_out_ptr,
+                                        status_ptr or None, MEM_DEVICE, stream or None, device))
+
+
 def frames_to_gray(frames: np.ndarray, frame_format, device: int = 0) -> np.ndarray:
     """dis_frames_to_gray_u8 on a host array: u8 (H, W, C) or (n, H, W, C) frames
     of `frame_format` ("bgr", "rgb", "bgra", "rgba"; "gray" takes (H, W) or
@@ -718,15 +812,29 @@ class DenseInverseSearch:
         """dis_flow_to_init on raw device pointers, asynchronous on `stream`."""
         _check(lib().dis_flow_to_init(self._ctx, n, flow_ptr, planes_ptr, MEM_DEVICE, stream or None))
 
-    def track(self, frames):
+    def track(self, frames, accumulate: bool = False):
         """Generator over an iterable of u8 H x W frames: yields the flow of
         each consecutive pair, warm-started from the flow of the pair before
-        (the first pair is cold)."""
+        (the first pair is cold). accumulate=True yields (flow_k, acc_k,
+        valid_k) instead: acc_k is the float32 flow from the first frame to the
+        pair's second frame and valid_k its u8 map. acc_1 is the first pair's
+        flow (valid_1 all 255); after that acc_k, valid_k =
+        flow_compose(acc_{k-1}, flow_k, valid_a=valid_{k-1}), with flow_k in the
+        engine's flow_dtype as it is."""
         prev_frame, prev_flow = None, None
+        acc, valid = None, None
         for f in frames:
             if prev_frame is not None:
                 prev_flow = self.calc(prev_frame, f, init=prev_flow)
-                yield prev_flow
+                if not accumulate:
+                    yield prev_flow
+                else:
+                    if acc is None:
+                        acc = prev_flow.astype(np.float32)  # (exact for float16; a copy for float32)
+                        valid = np.full(prev_flow.shape[:-1], 255, np.uint8)
+                    else:
+                        acc, valid = flow_compose(acc, prev_flow, valid_a=valid, with_valid=True, device=self.device)
+                    yield prev_flow, acc, valid
             prev_frame = f
 
     def calc_bidir(self, I0: np.ndarray, I1: np.ndarray):
