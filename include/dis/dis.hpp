@@ -390,6 +390,38 @@ inline void flowCompose(const float* a, const half_bits* b, int n, int width, in
                            valid_out, where, stream, device));
 }
 
+// Untrusted vectors of n W x H (u,v) fields filled from the trusted ones by
+// push-pull (dis_flow_fill), on the GPU: a vector is trusted when it is valid
+// (not NaN, |c| < 1e9) and its mask byte, if a mask is given, is not 0
+// (flowConsistency's mask, flowCompose's valid_out); every other pixel gets the
+// bilinear upsample of the nearest coarser level that holds trusted data, and
+// level (optional) tells which: 0 = kept, l = from about 2^l pixels away, 255 =
+// the field has no trusted vector (it comes back as NaN). out may be flow
+// itself. Device pointers need flowFillWorkspace(n, width, height) bytes of
+// workspace, 8-byte aligned; host pointers need none. The half_bits overload
+// fills an F16 engine's flows into an F32 field (the C entry point takes any
+// two formats).
+inline size_t flowFillWorkspace(int n, int width, int height)
+{
+    size_t bytes = 0;
+    check(dis_flow_fill_workspace(n, width, height, &bytes));
+    return bytes;
+}
+inline void flowFill(const float* flow, int n, int width, int height, float* out, const uint8_t* mask = nullptr,
+                     uint8_t* level = nullptr, void* workspace = nullptr, dis_mem where = DIS_MEM_HOST,
+                     void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fill(flow, DIS_FLOW_F32, mask, n, width, height, out, DIS_FLOW_F32, level, workspace, where, stream,
+                        device));
+}
+inline void flowFill(const half_bits* flow, int n, int width, int height, float* out, const uint8_t* mask = nullptr,
+                     uint8_t* level = nullptr, void* workspace = nullptr, dis_mem where = DIS_MEM_HOST,
+                     void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fill(flow, DIS_FLOW_F16, mask, n, width, height, out, DIS_FLOW_F32, level, workspace, where, stream,
+                        device));
+}
+
 // n fields' points moved by their field (dis_flow_advect_points), on the GPU:
 // `count` (x, y) float pairs per field; a point outside the frame or on an
 // invalid vector stays where it is with status 0, else status 255. points_out

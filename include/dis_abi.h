@@ -623,6 +623,64 @@ dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int 
                                   const float* points, int count, float* points_out,
                                   uint8_t* status /* may be NULL */, dis_mem where, void* stream, int device);
 
+/* Untrusted flow vectors filled from trusted ones (added within ABI v8,
+ * additive; no context): validity-weighted push-pull (Gortler et al., "The
+ * Lumigraph", section 4) over n W x H (u,v) fields, the stage between
+ * "bidirectional flow + mask" (dis_flow_consistency, dis_flow_compose's
+ * valid_out) and applying the flow. Every f32 operation is separately rounded.
+ *   flow, out: n W x H (u,v) fields in the layout the engine writes, floats
+ *          (DIS_FLOW_F32) or halves (DIS_FLOW_F16, widened exactly first); the
+ *          two formats are independent;
+ *   mask (may be NULL): n*W*H bytes, nonzero = trusted;
+ *   level (may be NULL): n*W*H bytes, see below.
+ * Levels: level 0 is the field, W_0 x H_0 = W x H; W_{l+1} = (W_l + 1) / 2 and
+ * H likewise, until 1 x 1 at level L (L = 0 for a 1 x 1 field, 11 for 1080p).
+ * Trust: ok_0(x, y) = |u| < 1e9 && |v| < 1e9 (false for NaN) && (mask == NULL
+ * || its byte != 0).
+ * Pull, for l = 0 .. L-1: cell (X, Y) of level l+1 has the children c00 = (2X,
+ * 2Y), c01 = (2X+1, 2Y), c10 = (2X, 2Y+1), c11 = (2X+1, 2Y+1) of level l; a
+ * child outside W_l x H_l is not ok. c = the number of ok children;
+ * ok_{l+1} = c > 0. If ok: f = the first ok child's vector in that order;
+ * d_i = ok_i ? v_i - f : 0 per component (a select: an untrusted vector never
+ * enters arithmetic); m = f + ((d00 + d01) + (d10 + d11)) * k[c] with k[1] =
+ * 1.0f, k[2] = 0.5f, k[3] = the float with the bits 0x3eaaaaab, k[4] = 0.25f.
+ * (This form returns a constant exactly when all ok children are equal; a
+ * plain sum times 1/3 does not.)
+ * Empty field: if ok_L(0, 0) is false, every pixel of `out` gets the canonical
+ * quiet NaN (f32 bits 0x7fc00000, f16 bits 0x7e00) and `level` 255.
+ * Push, for l = L-1 .. 0, with g_L = m_L: for cell (x, y) of level l,
+ * g_l = ok_l ? m_l (level 0: the input vector) : r, where px = x >> 1,
+ * py = y >> 1, qx = clamp(px + (x & 1 ? 1 : -1), 0, W_{l+1} - 1), qy likewise;
+ * P = g_{l+1}(px, py), Q = g_{l+1}(qx, py), R = g_{l+1}(px, qy),
+ * S = g_{l+1}(qx, qy); h0 = P + 0.25f * (Q - P); h1 = R + 0.25f * (S - R);
+ * r = h0 + 0.25f * (h1 - h0): the bilinear 9/3/3/1 upsample in lerp form (every
+ * cell of g_{l+1} is defined, so no weights are needed).
+ * Output: a trusted pixel keeps its input vector in out_format (equal formats:
+ * the same bits; F16 -> F32: widened exactly; F32 -> F16: the engine's own
+ * narrowing); every other pixel gets g_0, narrowed once if out_format is F16.
+ * level: the smallest l with ok_l(x >> l, y >> l): 0 = kept, larger = the
+ * nearest trusted data is about 2^l pixels away (callers threshold it).
+ * Workspace: dis_flow_fill_workspace returns 8 * n * sum_{l=1..L} W_l * H_l
+ * bytes (0 for a 1 x 1 field, and `workspace` may then be NULL): required and
+ * 8-byte aligned for DIS_MEM_DEVICE, ignored for DIS_MEM_HOST; its contents are
+ * unspecified. `out` may be the very buffer `flow` when the formats are equal
+ * (each pixel's vector is read before it is written, by the same lane); every
+ * other overlap of out, level or workspace with flow, mask or each other is
+ * refused. Refused with DIS_ERR_INVALID_ARGUMENT, before any device call: a
+ * null flow, out or bytes; n, width or height < 1; width or height > 2^24;
+ * formats other than F32 / F16; an unknown `where`; an overlap the rule above
+ * does not allow; more work than one launch's grid holds; for DIS_MEM_DEVICE a
+ * missing or misaligned workspace or a field pointer not aligned to one (u,v)
+ * pair of its format (8 bytes F32, 4 bytes F16). Host pointers: synchronous,
+ * staged through HIP device `device`; device pointers: asynchronous on
+ * `stream`, three launches (five or more when level 5 exceeds one block's
+ * LDS: beyond about 4600 level-5 cells, as for 4K frames). */
+dis_status dis_flow_fill_workspace(int n, int width, int height, size_t* bytes);
+dis_status dis_flow_fill(const void* flow, int flow_format, const uint8_t* mask /* may be NULL */,
+                         int n, int width, int height,
+                         void* out, int out_format, uint8_t* level /* may be NULL */,
+                         void* workspace, dis_mem where, void* stream, int device);
+
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,
  * little-endian; channels 1 (depth), 2 (flow) or 4 (scene flow). Host only

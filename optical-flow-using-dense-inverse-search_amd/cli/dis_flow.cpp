@@ -40,7 +40,13 @@
 // the valid map along; with --bidir pair k's forward consistency mask gates
 // its taps (mask_b). With --flo it is written as
 // OF_<folder>/frame_NNNN_acc.flo, invalid vectors as NaN; the count of valid
-// pixels is printed either way).
+// pixels is printed either way), --fill (needs --bidir: the forward flow's
+// vectors that fail the consistency check are replaced by dis::flowFill's
+// push-pull from those that pass; also writes OF_<folder>/frame_NNNN_filled.flo
+// and the level each vector came from as the 8-bit grey frame_NNNN_fill.png, 0 =
+// kept. With --accumulate the accumulated field is filled after each
+// composition, its valid map as the mask, and goes on with every pixel valid;
+// the count line then also gives the number of filled pixels).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -78,7 +84,7 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K  --color  --accumulate"
+                 "--interp K  --color  --accumulate  --fill"
               << std::endl;
 }
 
@@ -103,7 +109,7 @@ int main(int argc, char** argv)
     bool bidir = false, warm_start = false, batch_given = false, warp = false;
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
     int interp = 0;
-    bool color = false, accumulate = false;
+    bool color = false, accumulate = false, fill = false;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -125,6 +131,8 @@ int main(int argc, char** argv)
             color = true;
         } else if (a == "--accumulate") {
             accumulate = true;
+        } else if (a == "--fill") {
+            fill = true;
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -171,6 +179,10 @@ int main(int argc, char** argv)
         return 2;
     }
     if (warm_start) batch = 1;
+    if (fill && !bidir) {
+        std::cerr << "--fill replaces the vectors that fail the forward-backward check: it needs --bidir" << std::endl;
+        return 2;
+    }
     struct stat sb;
     if (argc == 1 && ::stat(folder.c_str(), &sb) != 0) {  // no arguments and no default sequence here
         usage();
@@ -244,6 +256,14 @@ int main(int argc, char** argv)
             } else {
                 eng->calc_batch(n, I0.data(), I1.data(), flow.data());
             }
+            std::vector<float> filled;
+            std::vector<uint8_t> fill_level;
+            if (fill) {
+                filled.resize(flow.size());
+                fill_level.resize((size_t)n * W * H);
+                dis::flowFill(flow.data(), n, W, H, filled.data(), mask.data(), fill_level.data(), nullptr, DIS_MEM_HOST,
+                              nullptr, device);
+            }
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             std::vector<uint8_t> warped, inside;
@@ -297,8 +317,19 @@ int main(int argc, char** argv)
                     size_t cnt = 0;
                     for (size_t q = 0; q < px; ++q) cnt += acc_valid[q] != 0;
                     std::cout << "accumulate " << frame_name(folder, i0 + k) << ".png: " << cnt << " of " << px
-                              << " pixels followed from frame " << start << std::endl;
+                              << " pixels followed from frame " << start;
+                    if (fill) {  // in place: the untrusted vectors from the trusted ones, then all are valid
+                        dis::flowFill(acc.data(), 1, W, H, acc.data(), acc_valid.data(), nullptr, nullptr, DIS_MEM_HOST,
+                                      nullptr, device);
+                        acc_valid.assign(px, 255);
+                        std::cout << ", " << px - cnt << " filled";
+                    }
+                    std::cout << std::endl;
                     if (write_flo) dis::check(dis_write_flo((base + "_acc.flo").c_str(), acc.data(), W, H, 2));
+                }
+                if (fill) {
+                    dis::check(dis_write_flo((base + "_filled.flo").c_str(), filled.data() + (size_t)k * W * H * 2, W, H, 2));
+                    png::write_gray(base + "_fill.png", fill_level.data() + (size_t)k * W * H, W, H);
                 }
                 if (bidir) {
                     png::write_bgr(base + "_bw.png", bgr_bw.data() + (size_t)k * W * H * 3, W, H);

@@ -156,4 +156,51 @@ inline const char* check_points(int n, int count, size_t* points)
     return nullptr;
 }
 
+// The levels of dis_flow_fill's push-pull: level 0 is the W x H field, each
+// further level halves both sides (rounding up) until 1 x 1 at level L. The
+// workspace holds levels 1..L of every field, 8 bytes a cell: off[l] cells lie
+// before level l in a field's part (off[0] is unused), `cells` in all.
+constexpr int kMaxFillLevels = 25;  // sides up to 2^24: L <= 24
+struct FillLevels {
+    int L;
+    int w[kMaxFillLevels], h[kMaxFillLevels];
+    size_t off[kMaxFillLevels];
+    size_t cells;
+};
+inline void fill_levels(int width, int height, FillLevels* g)
+{
+    int l = 0;
+    g->w[0] = width, g->h[0] = height, g->off[0] = 0, g->cells = 0;
+    while (g->w[l] > 1 || g->h[l] > 1) {
+        g->w[l + 1] = (g->w[l] + 1) / 2, g->h[l + 1] = (g->h[l] + 1) / 2;
+        g->off[l + 1] = g->cells;
+        g->cells += (size_t)g->w[l + 1] * g->h[l + 1];
+        ++l;
+    }
+    g->L = l;
+}
+
+// Blocks of one tile pass of the fill over n fields (a block per 64 x 32 cells
+// of the pass's first level; level 0 has the most); -1 when they exceed a grid.
+constexpr int kFillTileW = 64, kFillTileH = 32;
+inline long long fill_tile_blocks(int n, int width, int height)
+{
+    const long long tx = ((long long)width + kFillTileW - 1) / kFillTileW;
+    const long long ty = ((long long)height + kFillTileH - 1) / kFillTileH;
+    if (n < 1 || tx * ty > 0x7fffffffLL / n) return -1;
+    return tx * ty * n;
+}
+
+// dis_flow_fill_workspace: the sizes of dis_flow_fill, then 8 * n * cells (the
+// grid limit keeps n * W * H below 2^42, so the product far below 2^63).
+inline const char* check_fill_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide)) return why;
+    if (fill_tile_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    FillLevels g;
+    fill_levels(width, height, &g);
+    *bytes = 8 * (size_t)n * g.cells;
+    return nullptr;
+}
+
 }  // namespace dis

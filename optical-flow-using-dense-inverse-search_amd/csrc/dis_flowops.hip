@@ -185,6 +185,49 @@ dis_status dis_flow_compose(const void* a, int a_format, const void* b, int b_fo
                                                            dvo, s); }, "flow composition");
 }
 
+dis_status dis_flow_fill_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_fill_workspace(n, width, height, bytes));
+    return DIS_OK;
+}
+
+dis_status dis_flow_fill(const void* flow, int flow_format, const uint8_t* mask, int n, int width, int height, void* out,
+                         int out_format, uint8_t* level, void* workspace, dis_mem where, void* stream, int device)
+{
+    if (!flow || !out) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    size_t ws_bytes = 0;
+    DIS_ARG(dis::check_fill_workspace(n, width, height, &ws_bytes));  // sizes and the grid limit
+    if (bad_format(flow_format) || bad_format(out_format))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "formats must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    const bool dev = where == DIS_MEM_DEVICE;
+    if (dev && ws_bytes && !workspace) return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers need a workspace");
+    if (dev && ws_bytes && (addr(workspace) & 7)) return fail(DIS_ERR_INVALID_ARGUMENT, "workspace must be 8-byte aligned");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8, osz = out_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    // (a null mask, a null level and a host call's workspace take no part)
+    const dis::NamedRange r[5] = {{addr(flow), px * fsz, "flow"}, {addr(mask), mask ? px : 0, "mask"},
+                                  {addr(out), px * osz, "out"}, {addr(level), level ? px : 0, "level"},
+                                  {addr(workspace), dev ? ws_bytes : 0, "workspace"}};
+    const dis::MayAlias may[1] = {{2, 0}};  // in place: out may be flow itself when their formats are equal
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint_or_same(r, 2, 5, may, flow_format == out_format ? 1 : 0, &why));
+    if (dev && ((addr(flow) & (fsz - 1)) || (addr(out) & (osz - 1))))
+        return fail(DIS_ERR_INVALID_ARGUMENT,
+                    "flow and out must be aligned to one (u,v) pair of their format (8 bytes f32, 4 bytes f16)");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dis::HostStage st(s, !dev);
+    const void* dflow = st.in(flow, px * fsz);
+    const uint8_t* dmask = st.in(mask, px);
+    void* dout = st.out(out, px * osz);
+    uint8_t* dlevel = st.out(level, px);
+    void* dws = dev ? workspace : st.scratch(ws_bytes);
+    return st.finish([&] { return dis::launch_flow_fill(dflow, flow_format == DIS_FLOW_F16, dmask, n, width, height, dout,
+                                                        out_format == DIS_FLOW_F16, dlevel, dws, s); }, "flow fill");
+}
+
 dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int width, int height, const float* points,
                                   int count, float* points_out, uint8_t* status, dis_mem where, void* stream, int device)
 {

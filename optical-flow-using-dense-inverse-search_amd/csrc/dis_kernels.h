@@ -220,6 +220,19 @@ long long flow_advect_blocks(int n, int count);  // grid size of the launch
 hipError_t launch_flow_advect(const void* flow, int f16, int n, int W, int H, const float* points, int count,
                               float* points_out, uint8_t* status, hipStream_t s, Timing t = {});
 
+// Push-pull fill of the untrusted vectors of n W x H (u,v) fields (dis_fill.hip,
+// dis_flow_fill): k_fill_pull over levels 0..5, k_fill_top from there to 1 x 1
+// and back, k_fill_push down to `out` and `level` -- three launches, unless
+// level 5 and above exceed the top block's LDS (6,208 cells):
+// then a further pull and push pass over five more levels each. f16 / out_f16
+// != 0: that field holds __half2 vectors (4-byte aligned), else float2 (8-byte
+// aligned). mask and level may be null; out may be flow (equal formats).
+// workspace: 8 bytes per cell of levels 1..L of every field (dis_args.h,
+// fill_levels), 8-byte aligned; null for 1 x 1 fields. fill_tile_blocks(n, W, H)
+// (dis_args.h) >= 1.
+hipError_t launch_flow_fill(const void* flow, int f16, const uint8_t* mask, int n, int W, int H, void* out, int out_f16,
+                            uint8_t* level, void* workspace, hipStream_t s);
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

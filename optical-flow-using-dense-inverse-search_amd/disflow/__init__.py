@@ -107,6 +107,7 @@ EXPORTED_SYMBOLS = (
     "dis_flow_interp_workspace", "dis_flow_interp_u8",
     "dis_set_frame_format", "dis_frames_to_gray_u8",
     "dis_flow_compose", "dis_flow_advect_points",
+    "dis_flow_fill_workspace", "dis_flow_fill",
 )
 
 
@@ -237,6 +238,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_flow_compose"):  # (added within v8)
             L.dis_flow_compose.argtypes = [V, I, V, I, I, I, I, V, V, V, I, V, I, V, I]
             L.dis_flow_advect_points.argtypes = [V, I, I, I, I, V, I, V, V, I, V, I]
+        if hasattr(L, "dis_flow_fill"):  # (added within v8)
+            L.dis_flow_fill_workspace.argtypes = [I, I, I, P(Z)]
+            L.dis_flow_fill.argtypes = [V, I, V, I, I, I, V, I, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -535,6 +539,50 @@ def flow_compose_device(a_ptr: int, a_dtype, b_ptr: int, b_dtype, n: int, width:
     _check(lib().dis_flow_compose(a_ptr, a_fmt, b_ptr, b_fmt, n, width, height, valid_a_ptr or None,
                                   mask_b_ptr or None, out_ptr, o_fmt, valid_out_ptr or None, MEM_DEVICE,
                                   stream or None, device))
+
+
+def flow_fill_workspace(n: int, width: int, height: int) -> int:
+    """Bytes of device workspace dis_flow_fill needs for n W x H fields on device
+    pointers: 8 per cell of the push-pull levels above the field (0 for 1 x 1)."""
+    b = ctypes.c_size_t(0)
+    _check(lib().dis_flow_fill_workspace(n, width, height, ctypes.byref(b)))
+    return int(b.value)
+
+
+def flow_fill(flow: np.ndarray, mask=None, out_dtype=np.float32, with_level: bool = False, device: int = 0):
+    """Untrusted vectors of flow fields replaced from the trusted ones by
+    push-pull (dis_flow_fill) on the GPU. flow: float32 or float16 (H, W, 2) or
+    (n, H, W, 2); mask: optional u8 (..., H, W), nonzero = trusted
+    (flow_consistency's mask, flow_compose's valid map); out_dtype: float32
+    (default) or float16. A trusted vector (not NaN, |c| < 1e9, mask byte not 0)
+    is kept; every other pixel gets the bilinear upsample of the nearest coarser
+    level that holds trusted data. A field without any trusted vector comes back
+    as NaN. with_level: also the u8 map (..., H, W) of the level each vector came
+    from: 0 = kept, l = from about 2^l pixels away, 255 = empty field."""
+    fl = np.asarray(flow)
+    f_fmt, o_fmt = _flow_format(fl.dtype), _flow_format(out_dtype)
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError(f"flow must be (H, W, 2) or (n, H, W, 2), not {fl.shape}")
+    m = _byte_plane(mask, fl.shape[:-1], "mask")
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    fl = np.ascontiguousarray(fl)
+    out = np.empty(fl.shape, _FLOW_DTYPES[o_fmt])
+    level = np.empty(fl.shape[:-1], np.uint8) if with_level else None
+    _check(lib().dis_flow_fill(_ptr(fl), f_fmt, None if m is None else _ptr(m), n, W, H, _ptr(out), o_fmt,
+                               _ptr(level) if with_level else None, None, MEM_HOST, None, device))
+    return (out, level) if with_level else out
+
+
+def flow_fill_device(flow_ptr: int, flow_dtype, n: int, width: int, height: int, out_ptr: int, workspace_ptr: int,
+                     out_dtype=np.float32, mask_ptr: int = 0, level_ptr: int = 0, stream: int = 0,
+                     device: int = 0) -> None:
+    """dis_flow_fill on raw device pointers, asynchronous on `stream`.
+    workspace_ptr: flow_fill_workspace(n, width, height) bytes, 8-byte aligned
+    (0 for 1 x 1 fields). out_ptr may be flow_ptr (equal dtypes): in place."""
+    f_fmt, o_fmt = _flow_format(flow_dtype), _flow_format(out_dtype)
+    _check(lib().dis_flow_fill(flow_ptr, f_fmt, mask_ptr or None, n, width, height, out_ptr, o_fmt, level_ptr or None,
+                               workspace_ptr or None, MEM_DEVICE, stream or None, device))
 
 
 def advect_points(points: np.ndarray, flow: np.ndarray, with_status: bool = False, device: int = 0):
@@ -860,6 +908,23 @@ class DenseInverseSearch:
             wfw, wbw = flow_convert(fw, np.float32, self.device), flow_convert(bw, np.float32, self.device)
         return (fw, bw, flow_consistency(wfw, wbw, alpha1, alpha2, device=self.device),
                 flow_consistency(wbw, wfw, alpha1, alpha2, device=self.device))
+
+    def calc_filled(self, I0: np.ndarray, I1: np.ndarray, alpha1: float = 0.01, alpha2: float = 0.5,
+                    with_level: bool = False):
+        """u8 H x W frames (host) -> the forward flow with every vector that fails
+        the forward-backward check replaced by push-pull from those that pass
+        (calc_filled_batch on one pair); with_level: (flow, level)."""
+        r = self.calc_filled_batch(I0[None], I1[None], alpha1, alpha2, with_level)
+        return (r[0][0], r[1][0]) if with_level else r[0]
+
+    def calc_filled_batch(self, I0: np.ndarray, I1: np.ndarray, alpha1: float = 0.01, alpha2: float = 0.5,
+                          with_level: bool = False):
+        """One calc_bidir_batch with its forward consistency mask, then
+        flow_fill(fw, mask) in the engine's flow_dtype: a dense forward flow
+        without occluded or inconsistent vectors. with_level: (flows, levels),
+        levels as flow_fill's."""
+        fw, _, mask, _ = self.calc_bidir_batch(I0, I1, consistency=True, alpha1=alpha1, alpha2=alpha2)
+        return flow_fill(fw, mask, out_dtype=self.flow_dtype, with_level=with_level, device=self.device)
 
     def interpolate(self, I0: np.ndarray, I1: np.ndarray, ts, return_fill: bool = False):
         """The frames between u8 H x W frames I0 and I1 at every time of `ts`
