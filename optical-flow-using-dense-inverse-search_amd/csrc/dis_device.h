@@ -249,4 +249,15 @@ __device__ __forceinline__ float sqrt_core(float x)
     return x == 0.0f ? x : y;
 }
 
+// v of the lane a DPP control names (one v_mov_b32_dpp, all rows and banks):
+// a quad_perm pattern, or a row control such as row_ror
+constexpr int kQuadXor1 = 0xB1;  // quad_perm [1,0,3,2]: lane i <-> lane i^1
+constexpr int kQuadXor2 = 0x4E;  // quad_perm [2,3,0,1]: lane i <-> lane i^2
+constexpr int kRowRor8 = 0x128;  // row_ror:8: lane i <-> lane i^8 within a 16-lane row
+template <int CTRL>
+__device__ __forceinline__ float quad_perm(float v)
+{
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+
 }  // namespace dis

@@ -141,10 +141,10 @@ dis_status enqueue_front(dis_ctx* c, const SubBatch& v, const uint8_t* I0, const
         if (c->debug) pa.write_l0 = 1;
         pa.zero = v.fb_count;
         pa.nzero = g.C + 1;
-        if (pyramid2_fits(pa))  // the two-kernel streaming pyramid (dis_pyramid.hip)
+        if (pa.levels >= 2)  // the two streaming kernels; C == 1: k_pyr1 (dis_pyramid.hip)
             DIS_HIP(launch_pyramid2(pa, v.n, v.s, timing(c, 0)));
         else
-            DIS_HIP(launch_pyramid(pa, v.n, v.s, timing(c, 0)));
+            DIS_HIP(launch_pyramid1(pa, v.n, v.s, timing(c, 0)));
         for (int l = pa.levels + 1; l <= g.C; ++l) DIS_HIP(launch_down2(g, l, v.P.img0, v.P.img1, v.n, v.s));
     } else {
         // (zeroed on every path: DIS_STAGE_FALLBACK reports them after any calc)

@@ -105,7 +105,7 @@ struct UpsampleArgs {
     double inv_sc;
 };
 
-// Fused pyramid (dis_frontback.hip): u8 -> levels 1..`levels` (and 0 if write_l0).
+// The pyramid (dis_pyramid.hip): u8 -> levels 1..`levels` (and 0 if write_l0).
 struct PyramidArgs {
     const uint8_t* I0;
     const uint8_t* I1;
@@ -114,18 +114,20 @@ struct PyramidArgs {
     float* img0;
     float* img1;
     long long plane_stride;
-    int levels;    // levels produced in-kernel, 1..6 (tile = 2^levels level-0 pixels)
+    int levels;    // levels produced by the pyramid kernels, 1..6 (min(C, 6))
     int write_l0;  // also store the level-0 magnitude plane
     long long off[kMaxLevels];  // plane offset per level
     int w[kMaxLevels];          // plane width per level
     int* zero;                  // nzero ints set to 0 by workgroup 0 (the searches' fallback counts)
     int nzero;
-    int dword_ok;               // I0/I1, stride, pair_stride and pad_left 4-byte aligned: dword row loads
-    int qword_ok;               // ... and 16-byte aligned, pad_left a multiple of 16: 16-byte row loads
+    // the next two 8-byte aligned: k_pyr12 reads them with one scalar load, and
+    // its register allocation, hence its whole instruction stream, follows
+    // from how the loads of nzero and of these two group
+    alignas(8) int qword_ok;    // I0/I1, stride, pair_stride and pad_left multiples of 16: 16-byte row loads
     int vec_st;                 // k_pyr12: level-1 / level-2 rows 16-byte aligned (W_2 % 4 == 0; set by launch_pyramid2)
 };
 
-// Fused densify + upsample + crop (dis_frontback.hip).
+// Fused densify + upsample + crop (dis_output.hip).
 struct OutputArgs {
     const float2* u;   // finest-level patch u (pre-offset)
     float2* flow;      // W x H x 2 output, pair stride W*H
@@ -141,11 +143,11 @@ struct OutputArgs {
     long long plane_stride;
 };
 
-hipError_t launch_pyramid(const PyramidArgs& a, int batch, hipStream_t s, Timing t = {});
-// the same planes by two streaming kernels (dis_pyramid.hip): levels 1-2 from
-// global memory, then levels 3..a.levels; needs a.levels >= 2
-bool pyramid2_fits(const PyramidArgs& a);
+// a.levels >= 2 (C >= 2): k_pyr12, levels 1-2 from global memory, then
+// k_pyr_tail_reg, levels 3..a.levels; a.levels == 1 (C == 1): k_pyr1. Either
+// returns hipErrorInvalidValue for the other's arguments.
 hipError_t launch_pyramid2(const PyramidArgs& a, int batch, hipStream_t s, Timing t = {});
+hipError_t launch_pyramid1(const PyramidArgs& a, int batch, hipStream_t s, Timing t = {});
 bool output_fits(const OutputArgs& a);
 // f16 != 0 (here and in launch_upsample): a.flow points at __half2 vectors
 // (DIS_FLOW_F16), written by the kernels' __half2 instantiations

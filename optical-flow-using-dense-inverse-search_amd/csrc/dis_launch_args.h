@@ -52,7 +52,7 @@ void set_search8_lanes(Search8Args* b, int lanes);
 // blocks, the most a search can list
 size_t fb_list_blocks(const LevelGeom& L);
 
-// u8 frame rows loadable `bytes` (4: PyramidArgs.dword_ok, 16: qword_ok) at a
+// u8 frame rows loadable `bytes` (16: PyramidArgs.qword_ok) at a
 // time: both bases, the strides and pad_left are multiples of it (one pair:
 // pair_stride is never applied)
 bool frame_rows_aligned(const void* I0, const void* I1, size_t stride, size_t pair_stride, int n, int pad_left,

@@ -181,7 +181,6 @@ PyramidArgs pyramid_args(const Geometry& g, const Planes& P, const uint8_t* I0, 
     pa.plane_stride = P.plane_stride;
     pa.levels = std::min(g.C, 6);
     pa.write_l0 = g.F == 0 ? 1 : 0;
-    pa.dword_ok = frame_rows_aligned(I0, I1, stride, pair_stride, n, g.pad_left, 4);
     pa.qword_ok = frame_rows_aligned(I0, I1, stride, pair_stride, n, g.pad_left, 16);
     for (int l = 0; l <= g.C; ++l) {
         pa.off[l] = P.plane_off[l];

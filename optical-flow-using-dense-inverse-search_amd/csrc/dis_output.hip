@@ -1,10 +1,5 @@
-// dis_frontback.hip -- the fused front and back ends of the DIS path.
-//
-// K1+K2 (k_pyramid): u8 frame -> padded (virtual) -> level-0 Sobel magnitude
-// -> every 2x-downsampled level up to min(C, 6), one launch for both frames of
-// a batch (src/main.cpp:139-160, 12-31). A workgroup owns a 2^L x 2^L tile of
-// level 0; intermediate levels live in LDS, only the levels the search reads
-// are written to HBM (level 0 only when F == 0 or in debug mode).
+// dis_output.hip -- the fused back end of the DIS path (the front end, the
+// pyramid, is dis_pyramid.hip).
 //
 // K4+K5 (k_output): densify the finest searched level (src/patch_grid.cpp:
 // 121-182) straight from the patch displacements into an LDS tile, then
@@ -21,344 +16,6 @@
 
 namespace dis {
 
-namespace {
-
-
-}  // namespace
-
-// grid: (Wp / T0, Hp / T0, 2 * batch), block 256; z = pair*2 + frame.
-// LEVELS (1..6) is a template parameter so every load loop has a compile-time
-// trip count and all of a thread's loads are in flight at once.
-// frames per pyramid workgroup: 1 (z = 2 * pair + frame); both frames in one
-// 256-thread workgroup measured 7 % slower
-constexpr int kPyrNF = 1;
-constexpr int kPyrT = 128 * kPyrNF;  // threads per pyramid workgroup
-
-typedef short short2v __attribute__((ext_vector_type(2)));
-
-// 16-bit lanes (lo, hi) = (byte i, byte j) of the 8 bytes {w1:w0} (v_perm_b32)
-template <int I, int J>
-__device__ __forceinline__ short2v byte_pair(unsigned w0, unsigned w1)
-{
-    constexpr unsigned sel = 0x0c000c00u | (unsigned)I | ((unsigned)J << 16);
-    return __builtin_bit_cast(short2v, __builtin_amdgcn_perm(w1, w0, sel));
-}
-
-
-// LDS of one pyramid workgroup. u8 staging: tile column c of row r at byte
-// r * SR + CO + c, so the body columns 1..T0 start 4-byte aligned (dword
-// stores) and rows are aligned
-template <int LEVELS>
-struct PyrLds {
-    static constexpr int T0 = 1 << LEVELS, SS = T0 + 2, N1 = T0 / 2, CO = 3, SR = (SS + CO + 3) & ~3;
-    static constexpr int N2 = N1 / 2 > 0 ? N1 / 2 : 1;
-    alignas(16) uint8_t srcs[kPyrNF][SS * SR];
-    float bufs0[kPyrNF][N1 * N1];
-    float bufs1[kPyrNF][N2 * N2];
-};
-
-// Row loads of V bytes (4 or 16) for the tile body (columns 1..T0, aligned
-// source columns) + the two halo columns as bytes, for both frames
-template <int LEVELS, int V>
-struct PyrRows {
-    static constexpr int T0 = 1 << LEVELS, SS = T0 + 2;
-    static constexpr int Q = T0 / V > 0 ? T0 / V : 1, NBODY = kPyrNF * SS * Q, KB = (NBODY + kPyrT - 1) / kPyrT;
-    static constexpr int NH = kPyrNF * SS * 2, KH = (NH + kPyrT - 1) / kPyrT;
-    using VT = typename std::conditional<V == 16, uint4, unsigned>::type;
-    VT body[KB];
-    uint8_t halo[KH];
-};
-
-template <int LEVELS, int V>
-__device__ __forceinline__ void pyr_load_rows(const PyramidArgs& a, int tx, int ty, int pair, int fsel, int tid,
-                                              PyrRows<LEVELS, V>& R)
-{
-    using P = PyrRows<LEVELS, V>;
-    constexpr int SS = P::SS, Q = P::Q, T0 = P::T0;
-#pragma unroll
-    for (int k = 0; k < P::KB; ++k) {
-        const int i = min(tid + kPyrT * k, P::NBODY - 1);
-        const int f = i >= SS * Q, rem = i - f * SS * Q, r = rem / Q, j = rem - r * Q;
-        const int ys = clampi(reflect101(ty - 1 + r, a.Hp) - a.pt, 0, a.H - 1);
-        const uint8_t* in = ((f | fsel) ? a.I1 : a.I0) + (size_t)pair * a.pair_stride;
-        R.body[k] = *reinterpret_cast<const typename P::VT*>(in + (size_t)ys * a.stride + (tx - a.pl) + V * j);
-    }
-#pragma unroll
-    for (int k = 0; k < P::KH; ++k) {
-        const int i = min(tid + kPyrT * k, P::NH - 1);
-        const int f = i >= 2 * SS, rem = i - f * 2 * SS, r = rem >> 1, c = (rem & 1) ? T0 + 1 : 0;
-        const int ys = clampi(reflect101(ty - 1 + r, a.Hp) - a.pt, 0, a.H - 1);
-        const int xs = clampi(reflect101(tx - 1 + c, a.Wp) - a.pl, 0, a.W - 1);
-        const uint8_t* in = ((f | fsel) ? a.I1 : a.I0) + (size_t)pair * a.pair_stride;
-        R.halo[k] = in[(size_t)ys * a.stride + xs];
-    }
-}
-
-// unconditional stores: lanes past the end rewrite the last item (same
-// clamped index, same value) -- a conditional store let the compiler sink the
-// last load into the branch, after the wait for the others
-template <int LEVELS, int V>
-__device__ __forceinline__ void pyr_store_rows(PyrLds<LEVELS>& S, int tid, const PyrRows<LEVELS, V>& R)
-{
-    using P = PyrRows<LEVELS, V>;
-    using L = PyrLds<LEVELS>;
-    constexpr int SS = P::SS, Q = P::Q, T0 = P::T0;
-#pragma unroll
-    for (int k = 0; k < P::KB; ++k) {
-        const int i = min(tid + kPyrT * k, P::NBODY - 1);
-        const int f = i >= SS * Q, rem = i - f * SS * Q, r = rem / Q, j = rem - r * Q;
-        unsigned* d = reinterpret_cast<unsigned*>(&S.srcs[f][r * L::SR + L::CO + 1 + V * j]);  // 4-byte aligned
-        if constexpr (V == 16) {
-            d[0] = R.body[k].x;
-            d[1] = R.body[k].y;
-            d[2] = R.body[k].z;
-            d[3] = R.body[k].w;
-        } else {
-            d[0] = R.body[k];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < P::KH; ++k) {
-        const int i = min(tid + kPyrT * k, P::NH - 1);
-        const int f = i >= 2 * SS, rem = i - f * 2 * SS, r = rem >> 1, c = (rem & 1) ? T0 + 1 : 0;
-        S.srcs[f][r * L::SR + L::CO + c] = R.halo[k];
-    }
-}
-
-// whether a tile's body columns map onto aligned source columns (row loads)
-__device__ __forceinline__ bool pyr_row_loads(const PyramidArgs& a, int T0, int tx)
-{
-    return T0 >= 4 && a.dword_ok && tx - a.pl >= 0 && tx - a.pl + T0 <= a.W;
-}
-
-// u8 tile with a 1-pixel halo: replicate padding to Wp x Hp (floor/ceil
-// split) composed with Sobel's reflect-101 at the Wp x Hp border; tile column
-// c of row r at srcs[f][r * SR + CO + c]. Every lane computes its own row /
-// column indices (vector unit): with wave-uniform rows the per-row index and
-// 64-bit address arithmetic ran on the scalar unit, ~750 scalar instructions
-// per wave, which bounded the kernel.
-template <int LEVELS>
-__device__ __forceinline__ void pyr_stage(const PyramidArgs& a, PyrLds<LEVELS>& S, int tx, int ty, int pair, int fsel, int tid)
-{
-    using L = PyrLds<LEVELS>;
-    constexpr int T0 = L::T0, SS = L::SS, SR = L::SR, CO = L::CO;
-    const bool dw = pyr_row_loads(a, T0, tx);
-    if (dw && T0 >= 16 && a.qword_ok) {  // 16-byte row loads (3 per lane for a 64 x 64 tile of both frames)
-        PyrRows<LEVELS, 16> R;
-        pyr_load_rows(a, tx, ty, pair, fsel, tid, R);
-        pyr_store_rows(S, tid, R);
-    } else if (dw) {
-        PyrRows<LEVELS, 4> R;
-        pyr_load_rows(a, tx, ty, pair, fsel, tid, R);
-        pyr_store_rows(S, tid, R);
-    } else {
-        // any tile (padding columns, unaligned strides): one byte per item,
-        // 8 loads in flight per lane (bounded registers)
-        constexpr int NI = kPyrNF * SS * SS, KI = (NI + kPyrT - 1) / kPyrT, G = 8;
-#pragma unroll 1
-        for (int k0 = 0; k0 < KI; k0 += G) {
-            uint8_t v[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int i = min(tid + kPyrT * (k0 + g), NI - 1);
-                const int f = i >= SS * SS, rem = i - f * SS * SS, r = rem / SS, c = rem - r * SS;
-                const int ys = clampi(reflect101(ty - 1 + r, a.Hp) - a.pt, 0, a.H - 1);
-                const int xs = clampi(reflect101(tx - 1 + c, a.Wp) - a.pl, 0, a.W - 1);
-                const uint8_t* in = ((f | fsel) ? a.I1 : a.I0) + (size_t)pair * a.pair_stride;
-                v[g] = in[(size_t)ys * a.stride + xs];
-            }
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int i = min(tid + kPyrT * (k0 + g), NI - 1);  // unconditional (see pyr_store_rows)
-                const int f = i >= SS * SS, rem = i - f * SS * SS, r = rem / SS, c = rem - r * SS;
-                S.srcs[f][r * SR + CO + c] = v[g];
-            }
-        }
-    }
-}
-
-// Level 1 (and level 0 when requested) from the staged u8 tile, then levels
-// 2..LEVELS from LDS (a barrier per level); the caller has synchronised after
-// staging and synchronises before the LDS is reused
-template <int LEVELS>
-__device__ __forceinline__ void pyr_compute(const PyramidArgs& a, PyrLds<LEVELS>& S, int tx, int ty, int pair, int fsel, int tid)
-{
-    using L = PyrLds<LEVELS>;
-    constexpr int T0 = L::T0, N1 = L::N1, SR = L::SR, CO = L::CO;
-#pragma unroll
-    for (int f = 0; f < kPyrNF; ++f) {
-    const uint8_t* src = S.srcs[f];
-    float* buf0 = S.bufs0[f];
-    float* planes = ((f | fsel) ? a.img1 : a.img0) + (size_t)pair * a.plane_stride;
-    // level 1 (and level 0 when requested). A work item is a 2x2 block of
-    // level-1 pixels = a 4x4 block of level-0 magnitudes read from a 6x6 u8
-    // window; the separable Sobel row sums R/S are shared by the 16 pixels.
-    constexpr int B1 = N1 >= 2 ? 2 : 1;  // level-1 block edge
-    constexpr int NB = N1 / B1;          // blocks per tile edge
-    constexpr int E0 = 2 * B1;           // level-0 block edge
-#pragma unroll
-    for (int k0 = 0; k0 < NB * NB; k0 += kPyrT) {
-        const int k = k0 + tid;
-        if (NB * NB % kPyrT != 0 && k >= NB * NB) break;
-        const int by = k / NB, bx = k - by * NB;
-        // Sobel in exact integer arithmetic: with u8 input, R = r - l and
-        // T = 2c + l + r are integers, gx = (2R1 + R0 + R2) / 8 and
-        // gy = (T2 - T0) / 8 exactly (the reference's float expressions have
-        // no rounding here), so gx^2 + gy^2 = N / 64 exactly for the integer
-        // N = k1^2 + k2^2 < 2^21, and sqrtf(N / 64) = sqrt_cr(N) / 8.
-        float m[E0][E0];
-        if constexpr (E0 == 4) {
-            // packed 16-bit lanes (exact: |values| <= 1020). Per window row and
-            // column c: X = (R, T) = (v[c+2] - v[c], 2 v[c+1] + v[c] + v[c+2]);
-            // per pixel: q = (k1, k2) = (2 R1 + R0 + R2, T2 - T0) = X1 (2,0) +
-            // X0 (1,-1) + X2, and N = k1^2 + k2^2 = dot2(q, q). The 6-byte row
-            // comes in as two dwords (4-byte aligned: SR and 4 bx); (v, v)
-            // broadcast pairs by v_perm.
-            const short2v c02 = {0, 2}, cm11 = {-1, 1}, c20 = {2, 0}, c1m1 = {1, -1};
-            short2v X[6][4];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                // window columns 4 bx .. 4 bx + 5 = bytes CO + 4 bx ..: the last
-                // byte of dword 4 bx, dword 4 bx + 4, the first byte of 4 bx + 8
-                const unsigned* row = reinterpret_cast<const unsigned*>(src + (E0 * by + r) * SR + E0 * bx);
-                const unsigned w0 = row[0], w1 = row[1], w2 = row[2];
-                static_assert(CO == 3, "window byte map");
-                const short2v B[6] = {byte_pair<3, 3>(w0, w1), byte_pair<4, 4>(w0, w1), byte_pair<5, 5>(w0, w1),
-                                      byte_pair<6, 6>(w0, w1), byte_pair<7, 7>(w0, w1), byte_pair<4, 4>(w1, w2)};
-#pragma unroll
-                for (int c = 0; c < 4; ++c) X[r][c] = B[c] * cm11 + (B[c + 1] * c02 + B[c + 2]);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const short2v q = X[r + 1][c] * c20 + (X[r][c] * c1m1 + X[r + 2][c]);
-                    int n;
-                    __asm__("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(n) : "v"(q));
-                    m[r][c] = sqrt_cr((float)n);  // 8 x the magnitude (scaled below, exactly)
-                }
-        } else {
-            int R[E0 + 2][E0], T[E0 + 2][E0];
-#pragma unroll
-            for (int r = 0; r < E0 + 2; ++r) {
-                int v[E0 + 2];
-#pragma unroll
-                for (int c = 0; c < E0 + 2; ++c) v[c] = src[(E0 * by + r) * SR + CO + E0 * bx + c];
-#pragma unroll
-                for (int c = 0; c < E0; ++c) {
-                    R[r][c] = v[c + 2] - v[c];
-                    T[r][c] = 2 * v[c + 1] + v[c] + v[c + 2];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < E0; ++r)
-#pragma unroll
-                for (int c = 0; c < E0; ++c) {
-                    const int k1 = 2 * R[r + 1][c] + R[r][c] + R[r + 2][c];
-                    const int k2 = T[r + 2][c] - T[r][c];
-                    m[r][c] = sqrt_cr((float)(k1 * k1 + k2 * k2));
-                }
-        }
-        // m holds 8 x the level-0 magnitude sqrtf(N / 64) = sqrt_cr(N) / 8:
-        // scaling by a power of two commutes with every rounding below (no
-        // underflow / overflow), so the level-1 mean ((m00+m01)+m10)+m11)*0.25
-        // of the scaled values equals that of the unscaled ones times 2^-5
-        if (a.write_l0) {
-            float* const p0 = planes + (size_t)ty * a.Wp + tx;  // uniform base, 32-bit lane offsets
-#pragma unroll
-            for (int r = 0; r < E0; ++r)
-#pragma unroll
-                for (int c = 0; c < E0; ++c) p0[(E0 * by + r) * a.Wp + E0 * bx + c] = m[r][c] * 0.125f;
-        }
-        float* const p1 = planes + a.off[1] + (size_t)(ty / 2) * a.w[1] + tx / 2;
-#pragma unroll
-        for (int i = 0; i < B1; ++i)
-#pragma unroll
-            for (int j = 0; j < B1; ++j) {
-                float s = m[2 * i][2 * j] + m[2 * i][2 * j + 1];
-                s = s + m[2 * i + 1][2 * j];
-                s = s + m[2 * i + 1][2 * j + 1];
-                const float l1 = s * 0.03125f;  // (s / 8) * 0.25, exact
-                const int y1 = B1 * by + i, x1 = B1 * bx + j;
-                buf0[y1 * N1 + x1] = l1;
-                p1[y1 * a.w[1] + x1] = l1;
-            }
-    }
-
-    }
-    // levels 2..LEVELS from LDS for both frames at once (one barrier per
-    // level), ping-pong bufs0 <-> bufs1
-#pragma unroll
-    for (int l = 2; l <= LEVELS; ++l) {
-        __syncthreads();
-        const int ns = T0 >> (l - 1), nd = ns / 2, nn = nd * nd;
-        for (int k = tid; k < kPyrNF * nn; k += kPyrT) {
-            const int f = k >= nn, kk = k - f * nn;
-            const float* cur = (l & 1) ? S.bufs1[f] : S.bufs0[f];
-            float* nxt = (l & 1) ? S.bufs0[f] : S.bufs1[f];
-            float* planes = ((f | fsel) ? a.img1 : a.img0) + (size_t)pair * a.plane_stride;
-            float* const pl = planes + a.off[l] + (size_t)(ty >> l) * a.w[l] + (tx >> l);
-            const int y = kk / nd, x = kk - y * nd;
-            const float* p = cur + (2 * y) * ns + 2 * x;
-            float s = p[0] + p[1];
-            s = s + p[ns];
-            s = s + p[ns + 1];
-            const float v = s * 0.25f;
-            nxt[kk] = v;
-            pl[y * a.w[l] + x] = v;
-        }
-    }
-}
-
-template <int LEVELS>
-__global__ void __launch_bounds__(kPyrT) __attribute__((amdgpu_waves_per_eu(8))) k_pyramid(PyramidArgs a)
-{
-    __shared__ PyrLds<LEVELS> S;
-    constexpr int T0 = 1 << LEVELS;
-    const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-        for (int i = tid; i < a.nzero; i += blockDim.x) a.zero[i] = 0;
-    }
-    // XCD-aware tile order: the dispatcher deals linear block ids round-robin
-    // to the 8 XCDs; remap so each XCD gets a contiguous run of tiles along x
-    // and horizontally adjacent tiles share their 128-B rows in one L2.
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int nb = nbx * nby * gridDim.z;
-    const int lin = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
-    const int per = nb / 8;
-    const int t = (lin < per * 8) ? (lin % 8) * per + lin / 8 : lin;
-    // (divisions run on the vector unit: make the results provably uniform)
-    const int bx = __builtin_amdgcn_readfirstlane(t % nbx);
-    const int by = __builtin_amdgcn_readfirstlane((t / nbx) % nby);
-    const int bz = __builtin_amdgcn_readfirstlane(t / (nbx * nby));
-    const int tx = bx * T0, ty = by * T0;
-    // both frames of the tile in one workgroup (2x the loads in flight), or
-    // (kPyrNF 1) z = 2 * pair + frame
-    const int pair = kPyrNF == 2 ? bz : bz >> 1, fsel = kPyrNF == 2 ? 0 : bz & 1;
-    pyr_stage(a, S, tx, ty, pair, fsel, tid);
-    __syncthreads();
-    pyr_compute(a, S, tx, ty, pair, fsel, tid);
-}
-
-hipError_t launch_pyramid(const PyramidArgs& a, int batch, hipStream_t s, Timing t)
-{
-    const int T0 = 1 << a.levels;
-    if (a.levels < 1 || a.levels > 6 || a.Wp % T0 || a.Hp % T0) return hipErrorInvalidValue;
-    dim3 grid(a.Wp / T0, a.Hp / T0, batch * (2 / kPyrNF));
-    switch (a.levels) {
-        case 1: DIS_LAUNCH(t, k_pyramid<1>, grid, dim3(kPyrT), 0, s, a); break;
-        case 2: DIS_LAUNCH(t, k_pyramid<2>, grid, dim3(kPyrT), 0, s, a); break;
-        case 3: DIS_LAUNCH(t, k_pyramid<3>, grid, dim3(kPyrT), 0, s, a); break;
-        case 4: DIS_LAUNCH(t, k_pyramid<4>, grid, dim3(kPyrT), 0, s, a); break;
-        case 5: DIS_LAUNCH(t, k_pyramid<5>, grid, dim3(kPyrT), 0, s, a); break;
-        default: DIS_LAUNCH(t, k_pyramid<6>, grid, dim3(kPyrT), 0, s, a); break;
-    }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// back end
-// ---------------------------------------------------------------------------
 namespace {
 
 // full-resolution output tile per workgroup (measured: 64 rows beat 16 by

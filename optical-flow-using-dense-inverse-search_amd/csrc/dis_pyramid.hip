@@ -1,23 +1,27 @@
-// dis_pyramid.hip -- K1+K2 as two streaming kernels (no LDS staging of the
-// frames, no workgroup barriers on the bandwidth-heavy part):
+// dis_pyramid.hip -- the front end, K1+K2: u8 frames -> (virtual) pad ->
+// level-0 Sobel magnitude -> the 2x-downsampled levels 1..min(C, 6), both frames
+// of a batch (src/main.cpp:139-160, 12-31). Level 0 is stored only when F == 0
+// or in debug mode.
 //
-//   k_pyr12: u8 frame -> (virtual) pad -> level-0 Sobel magnitude -> levels 1
-//            and 2, straight from global memory. One lane = four consecutive
-//            level-2 pixels = 4x4 blocks of level-0 magnitudes from a 6x18 u8
-//            window (src/main.cpp:16-30, 139-160); a wave covers 256
-//            consecutive level-2 pixels of one row, so its u8 row loads are
-//            one 16-byte load per lane (1 KB contiguous) and the window's halo
-//            columns come from the neighbour lanes (DPP wave shifts); its
-//            level-1 and level-2 stores are 16-byte stores.
-//   k_pyr_tail: levels 3..L (L <= 6) from level 2, one wave per 2^(L-2)
-//            square of level-2 pixels, intermediate levels in LDS.
+// C >= 2, two streaming kernels (no LDS staging of the frames, no workgroup
+// barriers):
+//   k_pyr12: levels 0, 1 and 2 straight from global memory. One lane = four
+//            consecutive level-2 pixels = 4x4 blocks of level-0 magnitudes from
+//            a 6x18 u8 window; a wave covers 256 consecutive level-2 pixels of
+//            one row, so its u8 row loads are one 16-byte load per lane (1 KB
+//            contiguous) and the window's halo columns come from the neighbour
+//            lanes (DPP wave shifts); its level-1 and level-2 stores are
+//            16-byte stores.
+//   k_pyr_tail_reg<L>: levels 3..L (L <= 6) from level 2, one wave per pair of
+//            16 x 16 squares of level-2 pixels, the levels passed between
+//            lanes in registers.
+// C == 1:
+//   k_pyr1:  levels 0 and 1, one workgroup per 2 x 2 tile of level 0.
 //
-// Arithmetic is that of k_pyramid (dis_frontback.hip) and of the oracle:
-// integer Sobel (exact for u8 input), the magnitude sqrtf(N / 64) as
-// sqrt_cr(N) / 8 (correctly rounded), 2x2 means (((a + b) + c) + d) * 0.25
-// with a, b the top row -- bit-identical planes.
-#include <type_traits>
-
+// Arithmetic is that of the oracle in every kernel: integer Sobel (exact for
+// u8 input), the magnitude sqrtf(N / 64) as sqrt_cr(N) / 8 (correctly
+// rounded), 2x2 means (((a + b) + c) + d) * 0.25 with a, b the top row --
+// bit-identical planes.
 #include "dis_device.h"
 #include "dis_kernels.h"
 
@@ -27,7 +31,7 @@ namespace {
 
 typedef short short2p __attribute__((ext_vector_type(2)));
 
-// 16-bit lanes (lo, hi) = (byte I, byte J) of the 8 bytes {w1:w0}
+// 16-bit lanes (lo, hi) = (byte I, byte J) of the 8 bytes {w1:w0} (v_perm_b32)
 template <int I, int J>
 __device__ __forceinline__ short2p bytes2(unsigned w0, unsigned w1)
 {
@@ -73,16 +77,14 @@ struct Block4 {
     float l2;        // level 2
 };
 
-template <int R0, int NR>
-__device__ __forceinline__ void block4(const unsigned (&p)[NR], const unsigned (&m)[NR], const unsigned (&n)[NR],
-                                       Block4& o)
+__device__ __forceinline__ void block4(const unsigned (&p)[6], const unsigned (&m)[6], const unsigned (&n)[6], Block4& o)
 {
     // rows streamed: X of three window rows live at a time, the magnitudes of
     // one level-1 row (two level-0 rows) at a time (bounded registers)
     const short2p cm11 = {-1, 1}, c02 = {0, 2}, c20 = {2, 0}, c1m1 = {1, -1};
     short2p X[3][4];
     auto xrow = [&](int r, short2p (&x)[4]) {
-        const unsigned pr = p[R0 + r], mr = m[R0 + r], nr = n[R0 + r];
+        const unsigned pr = p[r], mr = m[r], nr = n[r];
         const short2p B[6] = {bytes2<3, 3>(pr, mr), bytes2<4, 4>(pr, mr), bytes2<5, 5>(pr, mr),
                               bytes2<6, 6>(pr, mr), bytes2<7, 7>(pr, mr), bytes2<4, 4>(mr, nr)};
 #pragma unroll
@@ -130,14 +132,13 @@ __device__ __forceinline__ void block4(const unsigned (&p)[NR], const unsigned (
 // per workgroup) or carries the halo rows in registers (2 / 4 rows per wave)
 // cut the bytes toward the algorithmic 300 MB per 32 pairs and lost time
 // (DRAM locality, not bytes, sets this kernel's rate).
-constexpr int kPyrRW = 1;  // level-2 rows per wave
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_pyr12(PyramidArgs a)
 {
-    constexpr int RW = kPyrRW, NR = 4 * RW + 2;
+    constexpr int NR = 6;  // window rows of the wave's level-2 row
     const int lane = threadIdx.x & 63;
-    const int W2 = a.w[2], H2 = a.Hp >> 2;
+    const int W2 = a.w[2];
     const int bx = blockIdx.x, bz = blockIdx.z, yb = blockIdx.y;
-    const int y2b = RW * yb;  // first level-2 row of the wave
+    const int y2 = yb;  // the wave's level-2 row
     const int g = bx * 64 + lane;  // lane's group of 4 level-2 pixels
     const int pair = bz >> 1, frame = bz & 1;
     if (bx == 0 && yb == 0 && bz == 0) {
@@ -158,7 +159,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
     unsigned d[4][NR], wl[NR], wr[NR];
     const uint8_t* rows[NR];
 #pragma unroll
-    for (int r = 0; r < NR; ++r) rows[r] = in + (size_t)src_row(a, 4 * y2b - 1 + r) * a.stride;
+    for (int r = 0; r < NR; ++r) rows[r] = in + (size_t)src_row(a, 4 * y2 - 1 + r) * a.stride;
     // every row's load in flight before any is consumed (no branch between
     // them): the 16-byte body loads of all lanes (lanes without a body read a
     // harmless in-bounds 16 bytes, W >= 16), then the byte gathers of the
@@ -211,15 +212,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
     if (g >= ng) return;
     float* planes = (frame ? a.img1 : a.img0) + (size_t)pair * a.plane_stride;
     const int np = min(4, W2 - 4 * g);  // level-2 pixels of this lane (the row's last group may be short)
-    auto level_row = [&](auto rr_c) {
-        constexpr int rr = decltype(rr_c)::value;  // level-2 row y2b + rr, window rows 4 rr ..
-        const int y2 = y2b + rr;
-        if (RW > 1 && y2 >= H2) return;
+    // the level-2 row's blocks and stores. (A lambda called once, not inline
+    // code: the compiler optimises its body on its own before inlining it, and
+    // the kernel's instruction stream follows from that.)
+    auto level_row = [&]() {
         float l1row[2][8], l2v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             Block4 o;
-            block4<4 * rr, NR>(q == 0 ? wl : d[q - 1], d[q], q == 3 ? wr : d[q + 1], o);
+            block4(q == 0 ? wl : d[q - 1], d[q], q == 3 ? wr : d[q + 1], o);
             if (a.write_l0 && q < np) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -256,20 +257,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_
                 }
         }
     };
-    level_row(std::integral_constant<int, 0>{});
-    if constexpr (RW > 1) level_row(std::integral_constant<int, 1>{});
-    if constexpr (RW > 2) level_row(std::integral_constant<int, 2>{});
-    if constexpr (RW > 3) level_row(std::integral_constant<int, 3>{});
+    level_row();
 }
 
-
-// k_pyr_tail_reg<L, TPW>: the same levels 3..L without LDS or barriers. One
-// wave per TPW horizontally adjacent 16 x 16 level-2 super-tiles; lane
+// k_pyr_tail_reg<L, TPW>: levels 3..L from level 2, without LDS or barriers.
+// One wave per TPW horizontally adjacent 16 x 16 level-2 super-tiles; lane
 // (qx, qy) = (lane & 7, lane >> 3) loads its 2 x 2 level-2 quad (two 8-byte
 // loads) and forms its level-3 pixel in-lane; level 4 / 5 / 6 take the 2 x 2
 // of the level below from the lanes 1 / 2 / 4 columns and 8 / 16 / 32 lanes
-// away (DPP quad_perm and row_ror:8, ds_bpermute for the rest) -- the same
-// ((a + b) + c) + d, a, b the top row, as k_pyr_tail, so bit-identical planes.
+// away (DPP quad_perm and row_ror:8, ds_bpermute for the rest), summed
+// ((a + b) + c) + d with a, b the top row.
 // Edge super-tiles (level-2 planes not a multiple of 16 wide / high, L < 6)
 // load 0 outside the plane and store only in-plane pixels, whose sources are
 // all in-plane (W_l = W_2 / 2^(l-2) exactly: pyramid2_fits).
@@ -277,9 +274,9 @@ namespace {
 template <int X>
 __device__ __forceinline__ float lane_xor(float v)
 {
-    if constexpr (X == 1) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));
-    else if constexpr (X == 2) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));
-    else if constexpr (X == 8) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, true));
+    if constexpr (X == 1) return quad_perm<kQuadXor1>(v);
+    else if constexpr (X == 2) return quad_perm<kQuadXor2>(v);
+    else if constexpr (X == 8) return quad_perm<kRowRor8>(v);
     else return __shfl_xor(v, X);
 }
 // 2x2 mean of the level below held at lanes (+0, +DX, +DY, +DX+DY); valid at the top-left lane
@@ -343,9 +340,10 @@ __global__ void __launch_bounds__(64) k_pyr_tail_reg(PyramidArgs a)
     }
 }
 
-// Whether the two-kernel pyramid applies: at least levels 1..2 in-kernel and
-// a padded size the level-2 grid and the tail tiles divide.
-bool pyramid2_fits(const PyramidArgs& a)
+// What the two kernels need: at least levels 1..2 in-kernel and a padded size
+// the level-2 grid and the tail tiles divide (make_geometry pads Wp, Hp to
+// multiples of 2^C, and levels <= C: true of every geometry with C >= 2).
+static bool pyramid2_fits(const PyramidArgs& a)
 {
     return a.levels >= 2 && a.levels <= 6 && a.Wp % (1 << a.levels) == 0 && a.Hp % (1 << a.levels) == 0;
 }
@@ -355,13 +353,12 @@ hipError_t launch_pyramid2(const PyramidArgs& a, int batch, hipStream_t s, Timin
     if (!pyramid2_fits(a)) return hipErrorInvalidValue;
     const int W2 = a.Wp >> 2, H2 = a.Hp >> 2;
     if (a.w[2] != W2) return hipErrorInvalidValue;
-    const int nrw = (H2 + kPyrRW - 1) / kPyrRW;  // waves per column
     PyramidArgs b = a;
     // level-1 rows start at 2 W_2 y floats, level-2 rows at W_2 y (plane
     // offsets are multiples of 4: Wp, Hp % 4 == 0): 16-byte stores need W_2 % 4 == 0
     // (with C = 2 or 3, Wp is only a multiple of 4 or 8)
     b.vec_st = W2 % 4 == 0;
-    DIS_LAUNCH(t, k_pyr12, dim3((W2 + 255) / 256, nrw, 2 * batch), dim3(64), 0, s, b);
+    DIS_LAUNCH(t, k_pyr12, dim3((W2 + 255) / 256, H2, 2 * batch), dim3(64), 0, s, b);
     if (a.levels >= 3) {
         constexpr int TPW = 2;  // 16 x 16 level-2 super-tiles per wave, loads in flight together
         const dim3 grid(((W2 + 15) / 16 + TPW - 1) / TPW, (H2 + 15) / 16, 2 * batch);
@@ -372,6 +369,140 @@ hipError_t launch_pyramid2(const PyramidArgs& a, int batch, hipStream_t s, Timin
             default: hipLaunchKernelGGL((k_pyr_tail_reg<6, TPW>), grid, dim3(64), 0, s, a); break;
         }
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// C == 1: k_pyr1, levels 0 and 1 only
+// ---------------------------------------------------------------------------
+// A workgroup owns one 2 x 2 tile of level 0 = one level-1 pixel: it stages
+// the tile's 4 x 4 u8 window (1-pixel halo) in LDS and lane 0 computes the tile
+// with the scalar integer Sobel. 128 threads for 16 bytes and one pixel is
+// wasteful; C == 1 is not a measured configuration.
+//
+// The kernel is the LEVELS == 1 instance of a general fused pyramid kernel
+// (2^L x 2^L tiles, levels in LDS) that no geometry with C >= 2 could reach.
+// It compiles to that instance's code, instruction for instruction, and four
+// leftovers of the general form are kept only because the compiler's output
+// follows them: the second staging round, the one-trip frame and work-item
+// loops of pyr1_compute, the LDS copy of the level-1 pixel, and the block remap
+// written out instead of a shared helper.
+constexpr int kPyr1T = 128;  // threads per workgroup
+
+// LDS: window column c of row r at byte r * SR + CO + c
+struct Pyr1Lds {
+    static constexpr int SS = 4, CO = 3, SR = 8;
+    alignas(16) uint8_t src[SS * SR];
+    float l1;
+};
+
+// Every lane computes its own row / column indices; loads before stores,
+// stores unconditional: lanes past the window's 16 bytes redo the last one
+// (same clamped index, same value), as does the whole second round
+__device__ __forceinline__ void pyr1_stage(const PyramidArgs& a, Pyr1Lds& S, int tx, int ty, int pair, int frame, int tid)
+{
+    constexpr int SS = Pyr1Lds::SS, CO = Pyr1Lds::CO, SR = Pyr1Lds::SR;
+    uint8_t v[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int i = min(tid + kPyr1T * g, SS * SS - 1), r = i / SS, c = i - r * SS;
+        const int ys = src_row(a, ty - 1 + r), xs = src_col(a, tx - 1 + c);
+        const uint8_t* in = (frame ? a.I1 : a.I0) + (size_t)pair * a.pair_stride;
+        v[g] = in[(size_t)ys * a.stride + xs];
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int i = min(tid + kPyr1T * g, SS * SS - 1), r = i / SS, c = i - r * SS;
+        S.src[r * SR + CO + c] = v[g];
+    }
+}
+
+// Level 1 (and level 0 when requested) from the staged window, by lane 0
+__device__ __forceinline__ void pyr1_compute(const PyramidArgs& a, Pyr1Lds& S, int tx, int ty, int pair, int frame, int tid)
+{
+    constexpr int CO = Pyr1Lds::CO, SR = Pyr1Lds::SR;
+    for (int f = 0; f < 1; ++f) {  // one frame, one work item (see above)
+        float* planes = (frame ? a.img1 : a.img0) + (size_t)pair * a.plane_stride;
+        for (int k = tid; k < 1; k += kPyr1T) {
+            // Sobel in exact integer arithmetic: with u8 input, R = r - l and
+            // T = 2c + l + r are integers, gx = (2R1 + R0 + R2) / 8 and
+            // gy = (T2 - T0) / 8 exactly (the reference's float expressions have
+            // no rounding here), so gx^2 + gy^2 = N / 64 exactly for the integer
+            // N = k1^2 + k2^2 < 2^21, and sqrtf(N / 64) = sqrt_cr(N) / 8.
+            int R[4][2], T[4][2];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                int w[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) w[c] = S.src[r * SR + CO + c];
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    R[r][c] = w[c + 2] - w[c];
+                    T[r][c] = 2 * w[c + 1] + w[c] + w[c + 2];
+                }
+            }
+            float m[2][2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const int k1 = 2 * R[r + 1][c] + R[r][c] + R[r + 2][c];
+                    const int k2 = T[r + 2][c] - T[r][c];
+                    m[r][c] = sqrt_cr((float)(k1 * k1 + k2 * k2));
+                }
+            // m holds 8 x the level-0 magnitude sqrtf(N / 64) = sqrt_cr(N) / 8:
+            // scaling by a power of two commutes with every rounding below (no
+            // underflow / overflow), so the level-1 mean ((m00+m01)+m10)+m11)*0.25
+            // of the scaled values equals that of the unscaled ones times 2^-5
+            if (a.write_l0) {
+                float* const p0 = planes + (size_t)ty * a.Wp + tx;
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) p0[r * a.Wp + c] = m[r][c] * 0.125f;
+            }
+            float* const p1 = planes + a.off[1] + (size_t)(ty / 2) * a.w[1] + tx / 2;
+            float s = m[0][0] + m[0][1];
+            s = s + m[1][0];
+            s = s + m[1][1];
+            const float l1 = s * 0.03125f;  // (s / 8) * 0.25, exact
+            S.l1 = l1;
+            *p1 = l1;
+        }
+    }
+}
+
+// grid (Wp / 2, Hp / 2, 2 * batch), block 128; z = 2 * pair + frame
+__global__ void __launch_bounds__(kPyr1T) __attribute__((amdgpu_waves_per_eu(8))) k_pyr1(PyramidArgs a)
+{
+    __shared__ Pyr1Lds S;
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+        for (int i = tid; i < a.nzero; i += blockDim.x) a.zero[i] = 0;
+    }
+    // XCD-aware tile order: the dispatcher deals linear block ids round-robin
+    // to the 8 XCDs; remap so each XCD gets a contiguous run of tiles along x
+    // and horizontally adjacent tiles share their 128-B rows in one L2.
+    const int nbx = gridDim.x, nby = gridDim.y;
+    const int nb = nbx * nby * gridDim.z;
+    const int lin = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
+    const int per = nb / 8;
+    const int t = (lin < per * 8) ? (lin % 8) * per + lin / 8 : lin;
+    // (divisions run on the vector unit: make the results provably uniform)
+    const int bx = __builtin_amdgcn_readfirstlane(t % nbx);
+    const int by = __builtin_amdgcn_readfirstlane((t / nbx) % nby);
+    const int bz = __builtin_amdgcn_readfirstlane(t / (nbx * nby));
+    const int tx = bx * 2, ty = by * 2;
+    const int pair = bz >> 1, frame = bz & 1;
+    pyr1_stage(a, S, tx, ty, pair, frame, tid);
+    __syncthreads();
+    pyr1_compute(a, S, tx, ty, pair, frame, tid);
+}
+
+hipError_t launch_pyramid1(const PyramidArgs& a, int batch, hipStream_t s, Timing t)
+{
+    if (a.levels != 1 || a.Wp % 2 || a.Hp % 2) return hipErrorInvalidValue;
+    DIS_LAUNCH(t, k_pyr1, dim3(a.Wp / 2, a.Hp / 2, 2 * batch), dim3(kPyr1T), 0, s, a);
     return hipGetLastError();
 }
 

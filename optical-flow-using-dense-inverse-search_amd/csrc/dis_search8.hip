@@ -63,17 +63,6 @@ constexpr int kCuPer = (kCuMax<LPP> + kThreads<LPP> - 1) / kThreads<LPP>;  // co
 constexpr int kFbWgs = 256;    // persistent k_search8_fb workgroups (grid-stride over the list)
 constexpr int kTileGroup = 8;  // tile rows per wave in flight
 
-// quad_perm DPP controls
-constexpr int kQuadXor1 = 0xB1;  // [1,0,3,2]
-constexpr int kQuadXor2 = 0x4E;  // [2,3,0,1]
-constexpr int kRowRor8 = 0x128;  // row_ror:8 (lane i <-> lane i^8 within a 16-lane row)
-
-template <int CTRL>
-__device__ __forceinline__ float quad_perm(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
 // lane -> (pixel-column slot q, patch-in-block pb) for LPP lanes per patch
 template <int LPP>
 __device__ __forceinline__ void lane_map(int tid, int& q, int& pb)

@@ -46,14 +46,12 @@ struct Lvl {
     int W, H;
 };
 
-__device__ __forceinline__ int clampi_(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ float* plane(const Lvl& L, int pair, int k)
 {
     return L.ws + (size_t)pair * L.ws_stride + (size_t)k * L.ws_plane;
 }
 
-// XCD-aware tile order (as k_pyramid): the dispatcher deals linear block ids
+// XCD-aware tile order (as k_search8): the dispatcher deals linear block ids
 // round-robin to the 8 XCDs; remapped, each XCD walks a contiguous run of
 // tiles, so the halos that neighbouring tiles share are fetched into one L2
 struct Tile {
@@ -96,10 +94,10 @@ __global__ void __launch_bounds__(256) k_vr_d0(Lvl L)
     const int W = L.W, H = L.H;
     const float* I0 = L.img0 + (size_t)pr * L.plane_stride;
     const float* r = I0 + (size_t)y * W;
-    const float gx = d5(r[clampi_(x - 2, 0, W - 1)], r[clampi_(x - 1, 0, W - 1)], r[clampi_(x + 1, 0, W - 1)],
-                        r[clampi_(x + 2, 0, W - 1)]);
-    const float gy = d5(I0[(size_t)clampi_(y - 2, 0, H - 1) * W + x], I0[(size_t)clampi_(y - 1, 0, H - 1) * W + x],
-                        I0[(size_t)clampi_(y + 1, 0, H - 1) * W + x], I0[(size_t)clampi_(y + 2, 0, H - 1) * W + x]);
+    const float gx = d5(r[clampi(x - 2, 0, W - 1)], r[clampi(x - 1, 0, W - 1)], r[clampi(x + 1, 0, W - 1)],
+                        r[clampi(x + 2, 0, W - 1)]);
+    const float gy = d5(I0[(size_t)clampi(y - 2, 0, H - 1) * W + x], I0[(size_t)clampi(y - 1, 0, H - 1) * W + x],
+                        I0[(size_t)clampi(y + 1, 0, H - 1) * W + x], I0[(size_t)clampi(y + 2, 0, H - 1) * W + x]);
     const size_t i = (size_t)y * W + x;
     plane(L, pr, P_I0X)[i] = gx;
     plane(L, pr, P_I0Y)[i] = gy;
@@ -146,13 +144,13 @@ __global__ void __launch_bounds__(256) k_vr_lin(Lvl L)
     for (int t = 0; t < NF; ++t) {
         const int k = min(tid + 256 * t, kFW * kFH - 1);
         const int ly = k / kFW, lx = k - ly * kFW;
-        f[t] = fl[(size_t)clampi_(y0 - 4 + ly, 0, H - 1) * W + clampi_(x0 - 4 + lx, 0, W - 1)];
+        f[t] = fl[(size_t)clampi(y0 - 4 + ly, 0, H - 1) * W + clampi(x0 - 4 + lx, 0, W - 1)];
     }
 #pragma unroll
     for (int t = 0; t < NG; ++t) {
         const int k = min(tid + 256 * t, kGW * kGH - 1);
         const int ly = k / kGW, lx = k - ly * kGW;
-        const size_t i = (size_t)clampi_(y0 - 2 + ly, 0, H - 1) * W + clampi_(x0 - 2 + lx, 0, W - 1);
+        const size_t i = (size_t)clampi(y0 - 2 + ly, 0, H - 1) * W + clampi(x0 - 2 + lx, 0, W - 1);
         gx0[t] = plane(L, pr, P_I0X)[i];
         gy0[t] = plane(L, pr, P_I0Y)[i];
     }
@@ -168,7 +166,7 @@ __global__ void __launch_bounds__(256) k_vr_lin(Lvl L)
     for (int t = 0; t < NF; ++t) {
         const int k = min(tid + 256 * t, kFW * kFH - 1);
         const int ly = k / kFW, lx = k - ly * kFW;
-        const int gx = clampi_(x0 - 4 + lx, 0, W - 1), gy = clampi_(y0 - 4 + ly, 0, H - 1);
+        const int gx = clampi(x0 - 4 + lx, 0, W - 1), gy = clampi(y0 - 4 + ly, 0, H - 1);
         float X = (float)gx + f[t].x, Y = (float)gy + f[t].y;
         X = fminf(fmaxf(X, -1.0f), (float)W);
         Y = fminf(fmaxf(Y, -1.0f), (float)H);
@@ -176,9 +174,9 @@ __global__ void __launch_bounds__(256) k_vr_lin(Lvl L)
         const int xa = (int)fx0, ya = (int)fy0;
         wfx[t] = X - fx0;
         wfy[t] = Y - fy0;
-        const int c0 = clampi_(xa, 0, W - 1), c1 = clampi_(xa + 1, 0, W - 1);
-        const float* r0 = I1 + (size_t)clampi_(ya, 0, H - 1) * W;
-        const float* r1 = I1 + (size_t)clampi_(ya + 1, 0, H - 1) * W;
+        const int c0 = clampi(xa, 0, W - 1), c1 = clampi(xa + 1, 0, W - 1);
+        const float* r0 = I1 + (size_t)clampi(ya, 0, H - 1) * W;
+        const float* r1 = I1 + (size_t)clampi(ya + 1, 0, H - 1) * W;
         ta[t] = r0[c0];
         tb[t] = r0[c1];
         tc[t] = r1[c0];
@@ -209,7 +207,7 @@ __global__ void __launch_bounds__(256) k_vr_lin(Lvl L)
     //    at the last column / row) over the tile + left column / top row
     for (int k = tid; k < kGW * kGH; k += 256) {
         const int ly = k / kGW, lx = k - ly * kGW;
-        const int ix = clampi_(x0 - 2 + lx, 0, W - 1) - x0 + 4, iy = clampi_(y0 - 2 + ly, 0, H - 1) - y0 + 4;
+        const int ix = clampi(x0 - 2 + lx, 0, W - 1) - x0 + 4, iy = clampi(y0 - 2 + ly, 0, H - 1) - y0 + 4;
         sWx[ly][lx] = d5(sI[iy][ix - 2], sI[iy][ix - 1], sI[iy][ix + 1], sI[iy][ix + 2]);
         sWy[ly][lx] = d5(sI[iy - 2][ix], sI[iy - 1][ix], sI[iy + 1][ix], sI[iy + 2][ix]);
     }

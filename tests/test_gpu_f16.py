@@ -148,7 +148,7 @@ def test_conversion_on_device_pointers(disflow_mod, src_off, dst_off):
 # 2. k_output against the oracle
 # ---------------------------------------------------------------------------
 # F = 1 interior-tile path (out_rows_f1): an output tile is 64 x 64 pixels at
-# F >= 1 (kOutTW x kOutTH, csrc/dis_frontback.hip) and takes that path when it
+# F >= 1 (kOutTW x kOutTH, csrc/dis_output.hip) and takes that path when it
 # lies inside W x H, none of its taps is clamped and the base allows the
 # two-pixel stores. The kernel has one instantiation per parity of
 # (pad_top - 1, pad_left - 1). Geometry (make_geometry, restated by

@@ -40,12 +40,14 @@ CASES = [
     (64, 48, 1, 0, 16, 3, 0.75, 1),       # ps 16
     (37, 29, 2, 2, 2, 3, 0.0, 1),         # ps 2, F == C
     (64, 64, 3, 0, 8, 0, 0.5, 1),         # iterations 0 (one update)
-    (1000, 200, 4, 1, 8, 6, 0.5, 1),      # pyramid dword row loads (stride, pad_left 4- not 16-byte aligned)
-    (432, 320, 4, 1, 8, 6, 0.5, 1),       # pyramid 16-byte row loads, 16 x 16 tiles
-    (420, 300, 4, 1, 8, 6, 0.5, 1),       # pad_left 6: byte row loads
+    (1000, 200, 4, 1, 8, 6, 0.5, 1),      # k_pyr12 byte path of unaligned frames (stride 1000, pad_left 4: qword_ok 0)
+    (432, 320, 4, 1, 8, 6, 0.5, 1),       # k_pyr12 16-byte body loads (stride 432, no padding: qword_ok 1)
+    (420, 300, 4, 1, 8, 6, 0.5, 1),       # k_pyr12 padding columns (pad_left 6, Wp 432), byte path
     (800, 600, 5, 2, 8, 8, 0.5, 1),       # C = 5: register pyramid tail, partial 16 x 16 super-tiles
     (100, 80, 2, 0, 8, 6, 0.5, 1),        # C = 2, W_2 = 25 odd: k_pyr12 scalar level-1/2 stores
     (104, 72, 3, 1, 8, 5, 0.5, 1),        # C = 3, W_2 = 26 = 2 mod 4: scalar stores, register tail level 3
+    (37, 29, 1, 0, 8, 4, 0.5, 1),         # C = 1, fast search: k_pyr1, ragged padding (38 x 30), level 0 written
+    (64, 48, 1, 1, 8, 4, 0.5, 1),         # C = 1, F = 1: k_pyr1 without level 0, k_output upsamples
 ]
 
 
@@ -104,8 +106,9 @@ def test_flat_image_singular_hessian(disflow_mod, oracle):
     _assert_bitexact(got, oracle.calc_u8(I0, I1, 2, 0, 8, 5, 0.5), "flow")
 
 
-def test_stage_dumps_bitexact(disflow_mod, oracle):
-    W, H, C, F, ps, it, ov = 200, 136, 3, 1, 8, 8, 0.625
+@pytest.mark.parametrize("W,H,C,F", [(200, 136, 3, 1), (37, 29, 1, 0)])  # k_pyr12 + tail; k_pyr1 on its own
+def test_stage_dumps_bitexact(disflow_mod, oracle, W, H, C, F):
+    ps, it, ov = 8, 8, 0.625
     I0, I1 = disflow_mod.synth_pair(5, W, H)
     eng = disflow_mod.DenseInverseSearch(_params(disflow_mod, C, F, ps, it, ov), W, H)
     eng.set_debug(True)

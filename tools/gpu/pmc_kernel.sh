@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters of one kernel (name substring $1) for a tools/ab.py variant ($2):
-#   CTRS="..." bash tools/gpu/pmc_kernel.sh k_pyramid lib.so:streams=1
+#   CTRS="..." bash tools/gpu/pmc_kernel.sh k_pyr12 lib.so:streams=1
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 CTRS=${CTRS:-SQ_WAVES SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE}
 timeout -k 10 90 rocprofv3 --pmc $CTRS --output-format csv -d $R/gpurun_out/pmck -o run -- python3 $R/tools/ab.py $2 --rounds 1 --steps 2 > $R/gpurun_out/pmck.log 2>&1 || { tail -5 $R/gpurun_out/pmck.log; exit 1; }
