@@ -71,6 +71,13 @@ inline int channels(FrameFormat f) { return f == FrameFormat::GRAY8 ? 1 : (f == 
 // what flowWarp does with a target outside the frame (dis_border)
 enum class Border { REPLICATE = DIS_BORDER_REPLICATE, ZERO = DIS_BORDER_ZERO };
 
+// the parametric model dis::fitMotion fits (dis_motion_model)
+enum class MotionModel {
+    TRANSLATION = DIS_MOTION_TRANSLATION,
+    SIMILARITY = DIS_MOTION_SIMILARITY,
+    AFFINE = DIS_MOTION_AFFINE
+};
+
 class Error : public std::runtime_error {
 public:
     Error(dis_status s, const std::string& what) : std::runtime_error(what), status_(s) {}
@@ -420,6 +427,52 @@ inline void flowFill(const half_bits* flow, int n, int width, int height, float*
 {
     check(dis_flow_fill(flow, DIS_FLOW_F16, mask, n, width, height, out, DIS_FLOW_F32, level, workspace, where, stream,
                         device));
+}
+
+// The global motion of n W x H (u,v) fields (dis_flow_fit_motion), on the GPU:
+// six floats per field, u = p0 + p1 x + p2 y and v = p3 + p4 x + p5 y over pixel
+// indices, fitted to the trusted vectors (valid, mask byte not 0) by least
+// squares and refitted `iterations` times on those within `threshold` pixels
+// of the previous fit; NaN when a fit fails. info (optional): per field
+// {1 fitted / 0 failed, trusted, fitted, agree}; inliers (optional): 255 where a
+// trusted vector agrees with the result. Device pointers need
+// fitMotionWorkspace(n, width, height) bytes of workspace, 8-byte aligned; host
+// pointers need none. The half_bits overload reads an F16 engine's flows.
+inline size_t fitMotionWorkspace(int n, int width, int height)
+{
+    size_t bytes = 0;
+    check(dis_flow_fit_motion_workspace(n, width, height, &bytes));
+    return bytes;
+}
+inline void fitMotion(const float* flow, int n, int width, int height, float* params,
+                      MotionModel model = MotionModel::AFFINE, int iterations = 3, float threshold = 1.0f,
+                      const uint8_t* mask = nullptr, uint32_t* info = nullptr, uint8_t* inliers = nullptr,
+                      void* workspace = nullptr, dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fit_motion(flow, DIS_FLOW_F32, mask, n, width, height, static_cast<int>(model), iterations, threshold,
+                              params, info, inliers, workspace, where, stream, device));
+}
+inline void fitMotion(const half_bits* flow, int n, int width, int height, float* params,
+                      MotionModel model = MotionModel::AFFINE, int iterations = 3, float threshold = 1.0f,
+                      const uint8_t* mask = nullptr, uint32_t* info = nullptr, uint8_t* inliers = nullptr,
+                      void* workspace = nullptr, dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fit_motion(flow, DIS_FLOW_F16, mask, n, width, height, static_cast<int>(model), iterations, threshold,
+                              params, info, inliers, workspace, where, stream, device));
+}
+
+// The fields of n motion models (dis_motion_to_flow): what flowWarp needs for
+// the stabilised frame and flowCompose for the camera path. A model with a
+// parameter that is not finite gives a NaN field.
+inline void motionToFlow(const float* params, int n, int width, int height, float* out, dis_mem where = DIS_MEM_HOST,
+                         void* stream = nullptr, int device = 0)
+{
+    check(dis_motion_to_flow(params, n, width, height, out, DIS_FLOW_F32, where, stream, device));
+}
+inline void motionToFlow(const float* params, int n, int width, int height, half_bits* out, dis_mem where = DIS_MEM_HOST,
+                         void* stream = nullptr, int device = 0)
+{
+    check(dis_motion_to_flow(params, n, width, height, out, DIS_FLOW_F16, where, stream, device));
 }
 
 // n fields' points moved by their field (dis_flow_advect_points), on the GPU:

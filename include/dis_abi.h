@@ -681,6 +681,95 @@ dis_status dis_flow_fill(const void* flow, int flow_format, const uint8_t* mask 
                          void* out, int out_format, uint8_t* level /* may be NULL */,
                          void* workspace, dis_mem where, void* stream, int device);
 
+/* Global motion from flow fields (added within ABI v8, additive; no context):
+ * a parametric model fitted to the trusted vectors of each of n W x H (u,v)
+ * fields by least squares and refitted `iterations` times on the vectors that
+ * agree with it, on the GPU; what a stabiliser needs of a flow. For every model
+ * the result is six floats per field in frame coordinates (x, y the pixel
+ * indices):
+ *   u(x, y) = (p0 + p1*x) + p2*y,   v(x, y) = (p3 + p4*x) + p5*y;
+ * translation has p1 = p2 = p4 = p5 = 0, similarity p1 = p5 and p4 = -p2.
+ *   flow:  n fields in the layout the engine writes, floats (DIS_FLOW_F32) or
+ *          halves (DIS_FLOW_F16, widened exactly first);
+ *   mask (may be NULL): n*W*H bytes, nonzero = trusted;
+ *   params: n*6 floats; info (may be NULL): n*4 words; inliers (may be NULL):
+ *          n*W*H bytes.
+ * The result is defined by its arithmetic, all of it f64 with every operation
+ * rounded on its own. cx = (W-1)/2, cy = (H-1)/2, x' = x - cx, y' = y - cy;
+ * (u, v) the pixel's vector widened to double (the products of two of these
+ * values are exact: only the additions round).
+ * Trusted: |u| < 1e9 && |v| < 1e9 on the f32 values (false for NaN) && (mask ==
+ * NULL || its byte != 0).
+ * Passes j = 0 .. iterations. Members of pass 0: the trusted pixels; of pass
+ * j >= 1: the trusted pixels with r2 <= T2 against the centred model c of pass
+ * j-1, T2 = (double)threshold * (double)threshold, eu = (c0 + c1*x') + c2*y',
+ * ev = (c3 + c4*x') + c5*y', ru = u - eu, rv = v - ev, r2 = ru*ru + rv*rv (the
+ * bound is inclusive; a NaN model has no members). A member contributes the
+ * twelve terms 1, x', y', x'x', x'y', y'y', u, x'u, y'u, v, x'v, y'v, every
+ * other pixel +0.0 twelve times.
+ * Order of summation, per field and term: pixels are indexed row-major,
+ * q = y*W + x, and cut into chunks of 16384. In a chunk, slot i (0..255) starts
+ * from +0.0 and adds the terms of pixels chunk*16384 + k*256 + i for k = 0..63
+ * in that order (pixels past the field's end: +0.0); the 256 slots are
+ * combined in eight rounds of adjacent pairs, a[i] = a[2i] + a[2i+1]; the chunk
+ * sums are added in increasing chunk order, starting from +0.0.
+ * Solve, with the sums S1 Sx Sy Sxx Sxy Syy Su Sxu Syu Sv Sxv Syv:
+ *   affine:      A = [[S1 Sx Sy] [Sx Sxx Sxy] [Sy Sxy Syy]], right-hand sides
+ *                (Su Sxu Syu) -> (c0 c1 c2) and (Sv Sxv Syv) -> (c3 c4 c5);
+ *   similarity:  unknowns (tx ty s r), u = tx + s*x' - r*y', v = ty + r*x' +
+ *                s*y'; A = [[S1 0 Sx -Sy] [0 S1 Sy Sx] [Sx Sy Sxx+Syy 0]
+ *                [-Sy Sx 0 Sxx+Syy]], right-hand side (Su Sv Sxu+Syv Sxv-Syu);
+ *                c = (tx s -r ty r s);
+ *   translation: S1*c0 = Su, S1*c3 = Sv; c1 = c2 = c4 = c5 = +0.0.
+ * By LDL^T without pivoting: for column j, d_j = A_jj - sum_{k<j} (L_jk*L_jk)*d_k
+ * and L_ij = (A_ij - sum_{k<j} (L_ik*L_jk)*d_k) / d_j, k ascending, each term
+ * subtracted in turn; forward substitution (rows ascending, k ascending, z_i -=
+ * L_ik*z_k), division by d, back substitution (rows descending, k ascending).
+ * The fit fails when some d_j > 2^-20 * A_jj is false (too few members,
+ * collinear members, none: a pivot that lost 20 bits of its diagonal element;
+ * a design rule); then all six c are NaN, and the later passes have no members
+ * and fail likewise.
+ * Output: p0 = (c0 - c1*cx) - c2*cy, p3 = (c3 - c4*cx) - c5*cy in f64, each of
+ * the six values rounded once to f32; a failed fit writes the bits 0x7fc00000
+ * six times. info = {1 fitted / 0 failed, trusted = S1 of pass 0, fitted = S1 of
+ * the last pass, agree}. inliers: 255 where a trusted pixel has r2 <= T2 against
+ * the final centred model (in f64, as above), else 0; agree is the count of
+ * those pixels, 0 when inliers is NULL.
+ * Workspace: dis_flow_fit_motion_workspace returns n * (chunks*12 + 16) * 8
+ * bytes, chunks = ceil(W*H / 16384): required and 8-byte aligned for
+ * DIS_MEM_DEVICE, ignored for DIS_MEM_HOST; its contents are unspecified.
+ * Refused with DIS_ERR_INVALID_ARGUMENT, before any device call: a null flow,
+ * params or bytes; n, width or height < 1; width or height > 2^24; W*H > 2^31;
+ * a format other than F32 / F16; an unknown model or `where`; iterations
+ * outside 0..16; a threshold that is not finite or negative; any overlap of
+ * params, info, inliers or the workspace with flow, mask or each other; more
+ * work than one launch's grid holds; for DIS_MEM_DEVICE a missing or misaligned
+ * workspace, a flow not aligned to one (u,v) pair of its format, params or info
+ * not 4-byte aligned. Host pointers: synchronous, staged through HIP device
+ * `device`; device pointers: asynchronous on `stream`, 2 * (iterations + 1)
+ * launches and one more for inliers, no allocation, no host synchronisation. */
+typedef enum dis_motion_model { DIS_MOTION_TRANSLATION = 0, DIS_MOTION_SIMILARITY = 1,
+                                DIS_MOTION_AFFINE = 2 } dis_motion_model;
+dis_status dis_flow_fit_motion_workspace(int n, int width, int height, size_t* bytes);
+dis_status dis_flow_fit_motion(const void* flow, int flow_format, const uint8_t* mask /* may be NULL */,
+                               int n, int width, int height, int model, int iterations, float threshold,
+                               float* params /* n*6 */, uint32_t* info /* n*4, may be NULL */,
+                               uint8_t* inliers /* n*W*H, may be NULL */,
+                               void* workspace, dis_mem where, void* stream, int device);
+
+/* The field of a motion model (added within ABI v8, additive; no context): n
+ * W x H fields from n*6 parameters, in f32 with every operation rounded on its
+ * own: u = (p0 + p1*(float)x) + p2*(float)y, v = (p3 + p4*(float)x) +
+ * p5*(float)y, narrowed with the engine's own conversion when out_format is
+ * DIS_FLOW_F16. A field is the canonical NaN everywhere (f32 bits 0x7fc00000,
+ * f16 bits 0x7e00) when any of its six parameters is not finite. This is how a
+ * model reaches dis_flow_warp_u8 (the stabilised frame) and dis_flow_compose
+ * (the camera path). Refusals as above (sizes, format, `where`, the grid, an
+ * overlap of out with params; for DIS_MEM_DEVICE out not aligned to one pair,
+ * params not 4-byte aligned). One launch. */
+dis_status dis_motion_to_flow(const float* params, int n, int width, int height,
+                              void* out, int out_format, dis_mem where, void* stream, int device);
+
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,
  * little-endian; channels 1 (depth), 2 (flow) or 4 (scene flow). Host only

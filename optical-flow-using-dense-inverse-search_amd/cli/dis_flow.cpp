@@ -46,7 +46,13 @@
 // and the level each vector came from as the 8-bit grey frame_NNNN_fill.png, 0 =
 // kept. With --accumulate the accumulated field is filled after each
 // composition, its valid map as the mask, and goes on with every pixel valid;
-// the count line then also gives the number of filled pixels).
+// the count line then also gives the number of filled pixels), --motion MODEL
+// (MODEL = translation, similarity or affine: the pair's global motion by
+// dis::fitMotion with its defaults, three refits within 1 px, written as
+// OF_<folder>/frame_NNNN_motion.txt: one line of the six parameters p0 .. p5,
+// u = p0 + p1 x + p2 y and v = p3 + p4 x + p5 y, "%.9g" each, nan where the fit
+// failed; with --bidir only the vectors that pass the consistency check are
+// fitted).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -84,7 +90,7 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K  --color  --accumulate  --fill"
+                 "--interp K  --color  --accumulate  --fill  --motion MODEL"
               << std::endl;
 }
 
@@ -110,6 +116,7 @@ int main(int argc, char** argv)
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
     int interp = 0;
     bool color = false, accumulate = false, fill = false;
+    std::string motion;  // --motion: the model's name (empty: no fit)
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -133,6 +140,8 @@ int main(int argc, char** argv)
             accumulate = true;
         } else if (a == "--fill") {
             fill = true;
+        } else if (a == "--motion" && i + 1 < argc) {
+            motion = argv[++i];
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -181,6 +190,15 @@ int main(int argc, char** argv)
     if (warm_start) batch = 1;
     if (fill && !bidir) {
         std::cerr << "--fill replaces the vectors that fail the forward-backward check: it needs --bidir" << std::endl;
+        return 2;
+    }
+    dis::MotionModel motion_model = dis::MotionModel::AFFINE;
+    if (motion == "translation") {
+        motion_model = dis::MotionModel::TRANSLATION;
+    } else if (motion == "similarity") {
+        motion_model = dis::MotionModel::SIMILARITY;
+    } else if (!motion.empty() && motion != "affine") {
+        std::cerr << "--motion MODEL: MODEL must be translation, similarity or affine" << std::endl;
         return 2;
     }
     struct stat sb;
@@ -264,6 +282,12 @@ int main(int argc, char** argv)
                 dis::flowFill(flow.data(), n, W, H, filled.data(), mask.data(), fill_level.data(), nullptr, DIS_MEM_HOST,
                               nullptr, device);
             }
+            std::vector<float> motion_params;
+            if (!motion.empty()) {
+                motion_params.resize((size_t)n * 6);
+                dis::fitMotion(flow.data(), n, W, H, motion_params.data(), motion_model, 3, 1.0f,
+                               bidir ? mask.data() : nullptr, nullptr, nullptr, nullptr, DIS_MEM_HOST, nullptr, device);
+            }
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             std::vector<uint8_t> warped, inside;
@@ -326,6 +350,14 @@ int main(int argc, char** argv)
                     }
                     std::cout << std::endl;
                     if (write_flo) dis::check(dis_write_flo((base + "_acc.flo").c_str(), acc.data(), W, H, 2));
+                }
+                if (!motion.empty()) {
+                    const float* m = motion_params.data() + (size_t)k * 6;
+                    char line[128];
+                    std::snprintf(line, sizeof line, "%.9g %.9g %.9g %.9g %.9g %.9g\n", m[0], m[1], m[2], m[3], m[4], m[5]);
+                    std::FILE* f = std::fopen((base + "_motion.txt").c_str(), "w");
+                    if (!f || std::fputs(line, f) < 0 || std::fclose(f) != 0)
+                        throw std::runtime_error("cannot write " + base + "_motion.txt");
                 }
                 if (fill) {
                     dis::check(dis_write_flo((base + "_filled.flo").c_str(), filled.data() + (size_t)k * W * H * 2, W, H, 2));

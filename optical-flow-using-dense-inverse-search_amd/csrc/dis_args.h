@@ -203,4 +203,51 @@ inline const char* check_fill_workspace(int n, int width, int height, size_t* by
     return nullptr;
 }
 
+// dis_flow_fit_motion sums a field in chunks of 16384 pixels (row-major), a
+// block per chunk and field; the last chunk of a field may be partial.
+constexpr int kMotionChunk = 16384;
+constexpr long long kMaxMotionPixels = 1ll << 31;  // a field's pixel index stays below 2^31 + one chunk
+constexpr int kMotionTerms = 12;                   // sums of one chunk
+constexpr int kMotionHead = 16;                    // doubles a field's part of the workspace begins with (the model)
+inline long long motion_chunks(int width, int height)
+{
+    return ((long long)width * height + kMotionChunk - 1) / kMotionChunk;
+}
+
+// Blocks of one accumulation pass over n fields; -1 when they exceed a grid.
+inline long long motion_blocks(int n, int width, int height)
+{
+    const long long c = motion_chunks(width, height);
+    if (n < 1 || c < 1 || c > 0x7fffffffLL / n) return -1;
+    return c * n;
+}
+
+// Blocks of dis_motion_to_flow's launch over n fields (256 lanes a block, a
+// lane per 4 pixels of a row); -1 when they exceed a grid.
+inline long long motion_flow_blocks(int n, int width, int height)
+{
+    const long long rows = (long long)n * height, cw = ((long long)width + 3) / 4;
+    if (n < 1 || cw < 1 || rows > 0x7fffffffLL * 256 / cw) return -1;
+    return (rows * cw + 255) / 256;
+}
+
+// The sizes of dis_motion_to_flow: the sides, the pixels and its grid.
+inline const char* check_motion_flow(int n, int width, int height)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide, kMaxMotionPixels)) return why;
+    if (motion_flow_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    return nullptr;
+}
+
+// dis_flow_fit_motion_workspace: the sizes of dis_flow_fit_motion (the sides,
+// the pixels, the grid of a pass), then per field the head and twelve doubles
+// per chunk (n * chunks fits a grid, so the product stays below 2^39).
+inline const char* check_motion_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide, kMaxMotionPixels)) return why;
+    if (motion_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    *bytes = (size_t)n * ((size_t)motion_chunks(width, height) * kMotionTerms + kMotionHead) * 8;
+    return nullptr;
+}
+
 }  // namespace dis

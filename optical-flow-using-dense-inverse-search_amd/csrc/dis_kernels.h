@@ -235,6 +235,20 @@ hipError_t launch_flow_advect(const void* flow, int f16, int n, int W, int H, co
 hipError_t launch_flow_fill(const void* flow, int f16, const uint8_t* mask, int n, int W, int H, void* out, int out_f16,
                             uint8_t* level, void* workspace, hipStream_t s);
 
+// Global motion of n W x H (u,v) fields (dis_motion.hip, dis_flow_fit_motion):
+// per pass k_motion_accum (a block per chunk of 16384 pixels and field) and
+// k_motion_solve (a block per field), iterations + 1 passes, then
+// k_motion_inliers when `inliers` is given. f16 != 0: the fields hold __half2
+// vectors (4-byte aligned), else float2 (8-byte aligned). mask, info and
+// inliers may be null. workspace: check_motion_workspace's bytes (dis_args.h),
+// 8-byte aligned. model: a dis_motion_model; motion_blocks(n, W, H) >= 1.
+hipError_t launch_fit_motion(const void* flow, int f16, const uint8_t* mask, int n, int W, int H, int model, int iterations,
+                             float threshold, float* params, unsigned* info, uint8_t* inliers, void* workspace,
+                             hipStream_t s);
+// The fields of n models of six parameters (dis_motion_to_flow): float2 or
+// (out_f16 != 0) __half2 vectors; motion_flow_blocks(n, W, H) >= 1.
+hipError_t launch_motion_flow(const float* params, int n, int W, int H, void* out, int out_f16, hipStream_t s);
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

@@ -58,6 +58,8 @@ FLOW_F32, FLOW_F16 = 0, 1  # dis_flow_format
 
 BORDER_REPLICATE, BORDER_ZERO = 0, 1  # dis_border
 
+MOTION_TRANSLATION, MOTION_SIMILARITY, MOTION_AFFINE = 0, 1, 2  # dis_motion_model
+
 FRAME_GRAY8, FRAME_BGR8, FRAME_RGB8, FRAME_BGRA8, FRAME_RGBA8 = range(5)  # dis_frame_format
 _FRAME_FORMATS = {"gray": FRAME_GRAY8, "bgr": FRAME_BGR8, "rgb": FRAME_RGB8, "bgra": FRAME_BGRA8,
                   "rgba": FRAME_RGBA8}
@@ -90,6 +92,9 @@ def _flow_format(dtype) -> int:
 _FLOW_DTYPES = {FLOW_F32: np.dtype(np.float32), FLOW_F16: np.dtype(np.float16)}
 _BORDERS = {"replicate": BORDER_REPLICATE, "zero": BORDER_ZERO, BORDER_REPLICATE: BORDER_REPLICATE,
             BORDER_ZERO: BORDER_ZERO}
+_MOTION_MODELS = {"translation": MOTION_TRANSLATION, "similarity": MOTION_SIMILARITY, "affine": MOTION_AFFINE,
+                  MOTION_TRANSLATION: MOTION_TRANSLATION, MOTION_SIMILARITY: MOTION_SIMILARITY,
+                  MOTION_AFFINE: MOTION_AFFINE}
 _INIT_KINDS = {"coarse": INIT_COARSE, "fullres": INIT_FULLRES, INIT_COARSE: INIT_COARSE, INIT_FULLRES: INIT_FULLRES}
 
 # Every symbol include/dis_abi.h declares (checked by tests/test_abi.py).
@@ -108,6 +113,7 @@ EXPORTED_SYMBOLS = (
     "dis_set_frame_format", "dis_frames_to_gray_u8",
     "dis_flow_compose", "dis_flow_advect_points",
     "dis_flow_fill_workspace", "dis_flow_fill",
+    "dis_flow_fit_motion_workspace", "dis_flow_fit_motion", "dis_motion_to_flow",
 )
 
 
@@ -241,6 +247,10 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_flow_fill"):  # (added within v8)
             L.dis_flow_fill_workspace.argtypes = [I, I, I, P(Z)]
             L.dis_flow_fill.argtypes = [V, I, V, I, I, I, V, I, V, V, I, V, I]
+        if hasattr(L, "dis_flow_fit_motion"):  # (added within v8)
+            L.dis_flow_fit_motion_workspace.argtypes = [I, I, I, P(Z)]
+            L.dis_flow_fit_motion.argtypes = [V, I, V, I, I, I, I, I, ctypes.c_float, V, V, V, V, I, V, I]
+            L.dis_motion_to_flow.argtypes = [V, I, I, I, V, I, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -583,6 +593,105 @@ def flow_fill_device(flow_ptr: int, flow_dtype, n: int, width: int, height: int,
     f_fmt, o_fmt = _flow_format(flow_dtype), _flow_format(out_dtype)
     _check(lib().dis_flow_fill(flow_ptr, f_fmt, mask_ptr or None, n, width, height, out_ptr, o_fmt, level_ptr or None,
                                workspace_ptr or None, MEM_DEVICE, stream or None, device))
+
+
+def _motion_args(model, iterations, threshold):
+    """(dis_motion_model, iterations, threshold) of fit_motion, checked as the library checks them."""
+    if isinstance(model, bool) or model not in _MOTION_MODELS:
+        raise ValueError(f"model must be 'translation', 'similarity' or 'affine', not {model!r}")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= iterations <= 16:
+        raise ValueError(f"iterations must be an integer in [0, 16], not {iterations!r}")
+    t = float(threshold)
+    if not (abs(t) <= float(np.finfo(np.float32).max) and t >= 0.0):  # (false for NaN; what a float holds)
+        raise ValueError(f"threshold must be finite and >= 0, not {threshold!r}")
+    return _MOTION_MODELS[model], int(iterations), t
+
+
+def fit_motion_workspace(n: int, width: int, height: int) -> int:
+    """Bytes of device workspace dis_flow_fit_motion needs for n W x H fields on
+    device pointers: n * (ceil(W * H / 16384) * 12 + 16) * 8."""
+    b = ctypes.c_size_t(0)
+    _check(lib().dis_flow_fit_motion_workspace(n, width, height, ctypes.byref(b)))
+    return int(b.value)
+
+
+def fit_motion(flow: np.ndarray, mask=None, model="affine", iterations: int = 3, threshold: float = 1.0,
+               return_info: bool = False, return_inliers: bool = False, device: int = 0):
+    """The global motion of flow fields (dis_flow_fit_motion) on the GPU: a
+    "translation", "similarity" or "affine" model fitted to the trusted vectors
+    by least squares, then refitted `iterations` times on the trusted vectors
+    within `threshold` pixels of the previous fit, so that moving objects and
+    outliers drop out. flow: float32 or float16 (H, W, 2) or (n, H, W, 2); mask:
+    optional u8 (..., H, W), nonzero = trusted (flow_consistency's mask,
+    flow_compose's valid map). Returns float32 params (6,) or (n, 6) with
+    u = p0 + p1 x + p2 y, v = p3 + p4 x + p5 y over pixel indices; NaN where the
+    fit failed (too few or collinear vectors). return_info: also uint32 (..., 4)
+    {1 fitted / 0 failed, trusted pixels, pixels of the last fit, pixels that
+    agree (0 without return_inliers)}; return_inliers: also the u8 plane
+    (..., H, W), 255 where a trusted vector lies within the threshold of the
+    result: its complement is the moving-object mask. Order: params, info,
+    inliers."""
+    fl = np.asarray(flow)
+    fmt = _flow_format(fl.dtype)
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError(f"flow must be (H, W, 2) or (n, H, W, 2), not {fl.shape}")
+    m = _byte_plane(mask, fl.shape[:-1], "mask")
+    mdl, its, thr = _motion_args(model, iterations, threshold)
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    lead = fl.shape[:-3]
+    fl = np.ascontiguousarray(fl)
+    params = np.empty(lead + (6,), np.float32)
+    info = np.empty(lead + (4,), np.uint32) if return_info else None
+    inl = np.empty(fl.shape[:-1], np.uint8) if return_inliers else None
+    _check(lib().dis_flow_fit_motion(_ptr(fl), fmt, None if m is None else _ptr(m), n, W, H, mdl, its, thr,
+                                     _ptr(params), _ptr(info) if return_info else None,
+                                     _ptr(inl) if return_inliers else None, None, MEM_HOST, None, device))
+    out = (params,) + ((info,) if return_info else ()) + ((inl,) if return_inliers else ())
+    return out if len(out) > 1 else params
+
+
+def fit_motion_device(flow_ptr: int, flow_dtype, n: int, width: int, height: int, params_ptr: int, workspace_ptr: int,
+                      model="affine", iterations: int = 3, threshold: float = 1.0, mask_ptr: int = 0,
+                      info_ptr: int = 0, inliers_ptr: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_flow_fit_motion on raw device pointers, asynchronous on `stream`: no
+    allocation and no host synchronisation, so it can be captured.
+    workspace_ptr: fit_motion_workspace(n, width, height) bytes, 8-byte aligned;
+    params_ptr: n * 6 float32; info_ptr: n * 4 uint32; inliers_ptr: n * W * H bytes."""
+    fmt = _flow_format(flow_dtype)
+    mdl, its, thr = _motion_args(model, iterations, threshold)
+    _check(lib().dis_flow_fit_motion(flow_ptr, fmt, mask_ptr or None, n, width, height, mdl, its, thr, params_ptr,
+                                     info_ptr or None, inliers_ptr or None, workspace_ptr or None, MEM_DEVICE,
+                                     stream or None, device))
+
+
+def motion_to_flow(params: np.ndarray, width: int, height: int, out_dtype=np.float32, device: int = 0) -> np.ndarray:
+    """The flow field of motion models (dis_motion_to_flow) on the GPU: params
+    float32 (6,) -> (H, W, 2), or (n, 6) -> (n, H, W, 2), u = (p0 + p1 x) + p2 y,
+    v = (p3 + p4 x) + p5 y in float32, as out_dtype (float32 or float16). A model
+    with a parameter that is not finite (a failed fit) gives a NaN field. The
+    result feeds flow_warp (the stabilised frame) and flow_compose."""
+    p = np.asarray(params)
+    o_fmt = _flow_format(out_dtype)
+    if p.dtype != np.float32:
+        raise ValueError(f"params dtype must be float32, not {p.dtype}")
+    if p.ndim not in (1, 2) or p.shape[-1] != 6 or p.size == 0:
+        raise ValueError(f"params must be (6,) or (n, 6), not {p.shape}")
+    if isinstance(width, bool) or isinstance(height, bool) or not isinstance(width, (int, np.integer)) or \
+            not isinstance(height, (int, np.integer)) or width < 1 or height < 1:
+        raise ValueError(f"width and height must be integers >= 1, not {width!r}, {height!r}")
+    n = p.shape[0] if p.ndim == 2 else 1
+    p = np.ascontiguousarray(p)
+    out = np.empty(p.shape[:-1] + (int(height), int(width), 2), _FLOW_DTYPES[o_fmt])
+    _check(lib().dis_motion_to_flow(_ptr(p), n, int(width), int(height), _ptr(out), o_fmt, MEM_HOST, None, device))
+    return out
+
+
+def motion_to_flow_device(params_ptr: int, n: int, width: int, height: int, out_ptr: int, out_dtype=np.float32,
+                          stream: int = 0, device: int = 0) -> None:
+    """dis_motion_to_flow on raw device pointers, asynchronous on `stream`."""
+    o_fmt = _flow_format(out_dtype)
+    _check(lib().dis_motion_to_flow(params_ptr, n, width, height, out_ptr, o_fmt, MEM_DEVICE, stream or None, device))
 
 
 def advect_points(points: np.ndarray, flow: np.ndarray, with_status: bool = False, device: int = 0):
