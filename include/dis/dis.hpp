@@ -19,6 +19,9 @@
 //   dis::flowCompose, dis::advectPoints
 //                             pair flows chained over a video: the flow from
 //                             frame 0 to frame k+1, and points followed
+//   dis::temporalDenoise, dis::denoiseWeights
+//                             a frame denoised from its neighbours, each warped
+//                             to it by its flow and weighted by the difference
 //   OpticalFlow::OpticalFlowClass
 //                             drop-in for the reference constructor with the
 //                             identical signature (include/optical_flow.hpp:43-54,
@@ -473,6 +476,41 @@ inline void motionToFlow(const float* params, int n, int width, int height, half
                          void* stream = nullptr, int device = 0)
 {
     check(dis_motion_to_flow(params, n, width, height, out, DIS_FLOW_F16, where, stream, device));
+}
+
+// Motion-compensated temporal denoising (dis_temporal_denoise_u8) of n W x H u8
+// images of `channels` (1, 3, 4) interleaved samples, on the GPU: each of the
+// k_neighbours (1..8) frames is warped to cur by its flow (cur -> neighbour k)
+// and blended in with weights[d], d the mean absolute difference to cur over the
+// pixel's 3 x 3 window. neighbours, flows and masks are host arrays of
+// k_neighbours pointers (host or device pointers as `where` says); masks or any
+// of its entries may be null; weights are 256 host floats in [0, 1], for
+// instance denoiseWeights(1.5 * the noise's sigma). support (optional): how many
+// neighbours took part at each pixel. The half_bits overload reads F16 flows.
+inline std::vector<float> denoiseWeights(float sigma)
+{
+    std::vector<float> table(256);
+    check(dis_denoise_weights(sigma, table.data()));
+    return table;
+}
+inline void temporalDenoise(const uint8_t* cur, const uint8_t* const* neighbours, int channels, const float* const* flows,
+                            int k_neighbours, int n, int width, int height, const float* weights, uint8_t* dst,
+                            const uint8_t* const* masks = nullptr, uint8_t* support = nullptr, size_t stride = 0,
+                            size_t image_stride = 0, dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_temporal_denoise_u8(cur, neighbours, stride, image_stride, channels,
+                                  reinterpret_cast<const void* const*>(flows), DIS_FLOW_F32, masks, k_neighbours, n, width,
+                                  height, weights, dst, support, where, stream, device));
+}
+inline void temporalDenoise(const uint8_t* cur, const uint8_t* const* neighbours, int channels,
+                            const half_bits* const* flows, int k_neighbours, int n, int width, int height,
+                            const float* weights, uint8_t* dst, const uint8_t* const* masks = nullptr,
+                            uint8_t* support = nullptr, size_t stride = 0, size_t image_stride = 0,
+                            dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_temporal_denoise_u8(cur, neighbours, stride, image_stride, channels,
+                                  reinterpret_cast<const void* const*>(flows), DIS_FLOW_F16, masks, k_neighbours, n, width,
+                                  height, weights, dst, support, where, stream, device));
 }
 
 // n fields' points moved by their field (dis_flow_advect_points), on the GPU:

@@ -770,6 +770,67 @@ dis_status dis_flow_fit_motion(const void* flow, int flow_format, const uint8_t*
 dis_status dis_motion_to_flow(const float* params, int n, int width, int height,
                               void* out, int out_format, dis_mem where, void* stream, int device);
 
+/* Motion-compensated temporal denoising of u8 images (added within ABI v8,
+ * additive; no context, like dis_flow_warp_u8; no reference counterpart): each
+ * of K neighbouring frames is warped to the current one by its flow and blended
+ * in with a per-pixel weight that falls with the photometric difference over a
+ * 3 x 3 window.
+ *   cur, neighbours[k]: n images of W x H pixels of `channels` (1, 3 or 4)
+ *          interleaved u8 samples each; one row stride `stride` and one image
+ *          stride `image_stride` in bytes for all (0 = dense), dis_flow_warp_u8's
+ *          conventions;
+ *   flows[k]: n W x H (u,v) fields, cur -> neighbour k, all F32 or all F16;
+ *   masks: NULL, or K entries each of which may be NULL; masks[k] holds n*W*H
+ *          bytes, nonzero = the vector is trusted;
+ *   weights: 256 floats in [0, 1], always host memory (dis_denoise_weights
+ *          makes the Gaussian table; any non-increasing table is as good);
+ *   dst:   n dense W x H x channels images; support (may be NULL): n W x H bytes.
+ * neighbours, flows and masks are host arrays of K pointers, read during the
+ * call; their entries are host or device pointers as `where` says. They and the
+ * table reach the kernel by value in its arguments, so the device call
+ * allocates nothing, copies nothing and does not synchronise (one launch; it
+ * can be captured in a graph). For pixel (x, y) of image i:
+ *   1. Wk, Vk = exactly the bytes dis_flow_warp_u8(neighbours[k], flows[k],
+ *      scale 1, DIS_BORDER_REPLICATE) writes to dst and valid: an invalid
+ *      vector gives 0 / 0, a target outside the frame the clamped sample and 0;
+ *   2. ok_k = Vk != 0 && (masks == NULL || masks[k] == NULL || its byte != 0);
+ *   3. D_k = the sum of |Wk(x', y', c) - cur(x', y', c)| over x' = x-1..x+1,
+ *      y' = y-1..y+1, each clamped to the frame, and all channels c;
+ *      idx = (D_k + cnt/2) / cnt in integers with cnt = 9*channels (0..255);
+ *   4. w_k = ok_k ? weights[idx] : +0.0f;
+ *   5. per channel num = sum over k ascending, from +0.0f, of
+ *      w_k * (float)(Wk_c - cur_c) (the difference an exact integer);
+ *      sw = the sum of w_k in the same order from +0.0f, den = 1.0f + sw;
+ *   6. r = (float)cur_c + num / den; the output byte is rintf(r) (ties to even)
+ *      clamped to [0, 255]; support = the number of k with ok_k && w_k > 0.
+ * Every f32 operation is separately rounded, integers are exact. So weights
+ * all 0 give dst == cur, neighbours equal to cur under zero flows give dst ==
+ * cur, and weights all 1 under zero flows give the rounded mean of the K + 1
+ * frames. Refused with DIS_ERR_INVALID_ARGUMENT, before any device call:
+ * dis_flow_warp_u8's list (a null cur, neighbours, flows, weights or dst; sizes;
+ * channels; flow_format; `where`; strides; the grid); k_neighbours outside
+ * 1..DIS_DENOISE_MAX_NEIGHBOURS; a null entry of neighbours or flows; a weight
+ * that is not finite or lies outside [0, 1]; any overlap of dst or support with
+ * cur, a neighbour, a flow, a mask or each other (dst cannot be cur: the window
+ * reads cur's surroundings); for DIS_MEM_DEVICE a flow not aligned to one (u,v)
+ * pair (8 bytes F32, 4 bytes F16). Image pointers need no alignment (aligned
+ * ones and W % 4 == 0 get wider accesses, same bytes). Host pointers:
+ * synchronous, staged through HIP device `device`; device pointers:
+ * asynchronous on `stream`.
+ * dis_denoise_weights (host only, no GPU): table[d] = (float)exp(-((double)d*d)
+ * / (2.0*(double)sigma*(double)sigma)), d = 0..255; refuses a null table and a
+ * sigma that is not finite or not > 0. */
+#define DIS_DENOISE_MAX_NEIGHBOURS 8
+dis_status dis_denoise_weights(float sigma, float table[256]);
+dis_status dis_temporal_denoise_u8(const uint8_t* cur, const uint8_t* const* neighbours /* K */, size_t stride,
+                                   size_t image_stride, int channels,
+                                   const void* const* flows /* K: field cur -> neighbour k */, int flow_format,
+                                   const uint8_t* const* masks /* NULL, or K entries each of which may be NULL */,
+                                   int k_neighbours, int n, int width, int height,
+                                   const float* weights /* 256, always host memory */,
+                                   uint8_t* dst, uint8_t* support /* may be NULL, n*W*H */,
+                                   dis_mem where, void* stream, int device);
+
 /* Middlebury .flo files (src/IO_flow.cpp:10-98): "PIEH", int32 width,
  * int32 height, width*height*channels float32 row-major interleaved,
  * little-endian; channels 1 (depth), 2 (flow) or 4 (scene flow). Host only

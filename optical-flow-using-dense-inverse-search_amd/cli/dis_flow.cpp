@@ -52,7 +52,13 @@
 // OF_<folder>/frame_NNNN_motion.txt: one line of the six parameters p0 .. p5,
 // u = p0 + p1 x + p2 y and v = p3 + p4 x + p5 y, "%.9g" each, nan where the fit
 // failed; with --bidir only the vectors that pass the consistency check are
-// fitted).
+// fitted), --denoise R SIGMA (after the pairs: every frame start .. end is
+// denoised in time by dis::temporalDenoise from the up to 2 R frames within R of
+// it that the range holds -- the end frames have fewer --, each warped to it by
+// the flow from it to that frame, which comes from the same engine in calls of
+// up to N pairs, with the table dis::denoiseWeights(SIGMA) and no masks; R in
+// [1, 4], SIGMA about 1.5 times the noise's standard deviation. Written as
+// OF_<folder>/frame_NNNN_denoised.png, 8-bit grey, colour with --color).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -90,7 +96,7 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K  --color  --accumulate  --fill  --motion MODEL"
+                 "--interp K  --color  --accumulate  --fill  --motion MODEL  --denoise R SIGMA"
               << std::endl;
 }
 
@@ -117,6 +123,9 @@ int main(int argc, char** argv)
     int interp = 0;
     bool color = false, accumulate = false, fill = false;
     std::string motion;  // --motion: the model's name (empty: no fit)
+    int denoise = 0;     // --denoise: the radius R (0: off)
+    float denoise_sigma = 0.0f;
+    bool denoise_given = false;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -142,6 +151,10 @@ int main(int argc, char** argv)
             fill = true;
         } else if (a == "--motion" && i + 1 < argc) {
             motion = argv[++i];
+        } else if (a == "--denoise" && i + 2 < argc) {
+            denoise = std::atoi(argv[++i]);
+            denoise_sigma = (float)std::atof(argv[++i]);
+            denoise_given = true;
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -179,6 +192,11 @@ int main(int argc, char** argv)
     if (batch < 1) batch = 1;
     if (interp < 0 || interp > 99) {
         std::cerr << "--interp K: K must lie in [0, 99]" << std::endl;
+        return 2;
+    }
+    if (denoise_given && (denoise < 1 || denoise > DIS_DENOISE_MAX_NEIGHBOURS / 2 || !(denoise_sigma > 0.0f) ||
+                          !(denoise_sigma < 1e30f))) {
+        std::cerr << "--denoise R SIGMA: R must lie in [1, 4] and SIGMA must be finite and > 0" << std::endl;
         return 2;
     }
     if (warm_start && ((batch_given && batch > 1) || bidir)) {
@@ -371,6 +389,57 @@ int main(int argc, char** argv)
                                                  H, 2));
                 }
                 std::cout << "finish " << frame_name(folder, i0 + k) << ".png" << std::endl;
+            }
+        }
+        if (denoise && eng) {  // --denoise: every frame of the range from its neighbours in time
+            const int C = color ? 3 : 1, T = end - start + 1;
+            const size_t fsz = (size_t)W * H * C, vsz = (size_t)W * H * 2;
+            std::vector<std::vector<uint8_t>> seq;
+            for (int t = 0; t < T; ++t) {
+                const std::string path = frame_name(folder, start + t) + ".png";
+                int w, h;
+                if (color) {
+                    png::Rgb f = png::read_rgb(path);
+                    w = f.width, h = f.height;
+                    seq.push_back(std::move(f.px));
+                } else {
+                    png::Gray f = png::read_gray(path);
+                    w = f.width, h = f.height;
+                    seq.push_back(std::move(f.px));
+                }
+                if (w != W || h != H) throw std::runtime_error("--denoise: frame sizes differ within the range");
+            }
+            const std::vector<float> table = dis::denoiseWeights(denoise_sigma);
+            std::vector<uint8_t> out(fsz);
+            for (int t = 0; t < T; ++t) {
+                std::vector<int> js;
+                for (int j = std::max(t - denoise, 0); j <= std::min(t + denoise, T - 1); ++j)
+                    if (j != t) js.push_back(j);
+                const int K = (int)js.size();
+                std::vector<float> flows((size_t)K * vsz);
+                for (int b = 0; b < K; b += batch) {  // the flows from frame t to its neighbours, up to `batch` a call
+                    const int n = std::min(batch, K - b);
+                    std::vector<uint8_t> I0((size_t)n * fsz), I1((size_t)n * fsz);
+                    for (int k = 0; k < n; ++k) {
+                        std::copy(seq[t].begin(), seq[t].end(), I0.begin() + (size_t)k * fsz);
+                        std::copy(seq[js[b + k]].begin(), seq[js[b + k]].end(), I1.begin() + (size_t)k * fsz);
+                    }
+                    eng->calc_batch(n, I0.data(), I1.data(), flows.data() + (size_t)b * vsz);
+                }
+                std::vector<const uint8_t*> nb;
+                std::vector<const float*> fl;
+                for (int k = 0; k < K; ++k) {
+                    nb.push_back(seq[js[k]].data());
+                    fl.push_back(flows.data() + (size_t)k * vsz);
+                }
+                dis::temporalDenoise(seq[t].data(), nb.data(), C, fl.data(), K, 1, W, H, table.data(), out.data(), nullptr,
+                                     nullptr, 0, 0, DIS_MEM_HOST, nullptr, device);
+                const std::string path = "OF_" + frame_name(folder, start + t) + "_denoised.png";
+                if (color)
+                    png::write_rgb(path, out.data(), W, H);
+                else
+                    png::write_gray(path, out.data(), W, H);
+                std::cout << "denoised " << frame_name(folder, start + t) << ".png from " << K << " frames" << std::endl;
             }
         }
     } catch (const std::exception& e) {

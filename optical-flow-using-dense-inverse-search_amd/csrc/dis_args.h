@@ -250,4 +250,70 @@ inline const char* check_motion_workspace(int n, int width, int height, size_t* 
     return nullptr;
 }
 
+// dis_temporal_denoise_u8: a block per 64 x 16 output pixels and image, up to 8
+// neighbours a call (their pointers travel in the kernel's arguments).
+constexpr int kDenoiseMaxNeighbours = 8;
+constexpr int kDenoiseTileW = 64, kDenoiseTileH = 16;
+
+// Blocks of the launch over n images; -1 when they exceed a grid (which also
+// keeps every byte count of the call far below 2^63).
+inline long long denoise_blocks(int n, int width, int height)
+{
+    const long long tx = ((long long)width + kDenoiseTileW - 1) / kDenoiseTileW;
+    const long long ty = ((long long)height + kDenoiseTileH - 1) / kDenoiseTileH;
+    if (n < 1 || tx < 1 || ty < 1 || tx * ty > 0x7fffffffLL / n) return -1;
+    return tx * ty * n;
+}
+
+// The sizes of dis_temporal_denoise_u8: the sides, the channels, the neighbour
+// count and the grid.
+inline const char* check_denoise_sizes(int k_neighbours, int n, int width, int height, int channels)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide)) return why;
+    if (channels != 1 && channels != 3 && channels != 4) return "channels must be 1, 3 or 4";
+    if (k_neighbours < 1 || k_neighbours > kDenoiseMaxNeighbours) return "k_neighbours must be in [1, 8]";
+    if (denoise_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    return nullptr;
+}
+
+// One entry of the weight table: in [0, 1] (false for NaN and the infinities).
+inline bool denoise_weight_ok(float w) { return w >= 0.0f && w <= 1.0f; }
+
+// The buffers of dis_temporal_denoise_u8 by address: cur and the K neighbours
+// (image_bytes each), the K flows (flow_bytes each), the K masks (pixels bytes
+// each; `masks` may be null, and so may any of its entries), dst (dst_bytes) and
+// support (pixels bytes, may be 0 = absent). No neighbour or flow may be null;
+// dst and support must be disjoint from every input and from each other. For
+// device pointers (flow_align = bytes of one (u,v) pair, else 0) every flow
+// must be aligned to a pair.
+inline const char* check_denoise_buffers(uintptr_t cur, const uintptr_t* neighbours, const uintptr_t* flows,
+                                         const uintptr_t* masks, int k_neighbours, size_t image_bytes,
+                                         size_t flow_bytes, size_t pixels, uintptr_t dst, size_t dst_bytes,
+                                         uintptr_t support, size_t flow_align, PairMessage* why)
+{
+    static const char* const nb[kDenoiseMaxNeighbours] = {"neighbours[0]", "neighbours[1]", "neighbours[2]", "neighbours[3]",
+                                                          "neighbours[4]", "neighbours[5]", "neighbours[6]", "neighbours[7]"};
+    static const char* const fl[kDenoiseMaxNeighbours] = {"flows[0]", "flows[1]", "flows[2]", "flows[3]",
+                                                          "flows[4]", "flows[5]", "flows[6]", "flows[7]"};
+    static const char* const mk[kDenoiseMaxNeighbours] = {"masks[0]", "masks[1]", "masks[2]", "masks[3]",
+                                                          "masks[4]", "masks[5]", "masks[6]", "masks[7]"};
+    if (k_neighbours < 1 || k_neighbours > kDenoiseMaxNeighbours) return "k_neighbours must be in [1, 8]";
+    NamedRange r[3 * kDenoiseMaxNeighbours + 3];
+    int m = 0;
+    r[m++] = {cur, image_bytes, "cur"};
+    for (int k = 0; k < k_neighbours; ++k) {
+        if (!neighbours[k] || !flows[k]) return "null entry in neighbours or flows";
+        if (flow_align && (flows[k] & (flow_align - 1)))
+            return "every flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)";
+        r[m++] = {neighbours[k], image_bytes, nb[k]};
+        r[m++] = {flows[k], flow_bytes, fl[k]};
+        const uintptr_t mp = masks ? masks[k] : 0;
+        r[m++] = {mp, mp ? pixels : 0, mk[k]};
+    }
+    const int nin = m;
+    r[m++] = {dst, dst_bytes, "dst"};
+    r[m++] = {support, support ? pixels : 0, "support"};
+    return check_disjoint(r, nin, m, why);
+}
+
 }  // namespace dis

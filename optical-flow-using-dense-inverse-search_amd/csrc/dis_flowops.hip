@@ -145,6 +145,58 @@ dis_status dis_flow_warp_u8(const uint8_t* src, size_t src_stride, size_t src_im
                                                         height, scale, zero, ddst, dvalid, s); }, "flow warp");
 }
 
+dis_status dis_denoise_weights(float sigma, float table[256])
+{
+    if (!table) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!std::isfinite(sigma) || !(sigma > 0.0f)) return fail(DIS_ERR_INVALID_ARGUMENT, "sigma must be finite and > 0");
+    const double s2 = 2.0 * (double)sigma * (double)sigma;
+    for (int d = 0; d < 256; ++d) table[d] = (float)std::exp(-((double)d * d) / s2);
+    return DIS_OK;
+}
+
+dis_status dis_temporal_denoise_u8(const uint8_t* cur, const uint8_t* const* neighbours, size_t stride,
+                                   size_t image_stride, int channels, const void* const* flows, int flow_format,
+                                   const uint8_t* const* masks, int k_neighbours, int n, int width, int height,
+                                   const float* weights, uint8_t* dst, uint8_t* support, dis_mem where, void* stream,
+                                   int device)
+{
+    if (!cur || !neighbours || !flows || !weights || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    if (bad_format(flow_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    DIS_ARG(dis::check_denoise_sizes(k_neighbours, n, width, height, channels));  // sizes, channels, K and the grid
+    dis::ImageStack im;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, stride, image_stride, &im));
+    for (int d = 0; d < 256; ++d)
+        if (!dis::denoise_weight_ok(weights[d])) return fail(DIS_ERR_INVALID_ARGUMENT, "weights must lie in [0, 1]");
+    const bool dev = where == DIS_MEM_DEVICE;
+    const int K = k_neighbours;
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    uintptr_t nb[dis::kDenoiseMaxNeighbours], fl[dis::kDenoiseMaxNeighbours], mk[dis::kDenoiseMaxNeighbours];
+    for (int k = 0; k < K; ++k) nb[k] = addr(neighbours[k]), fl[k] = addr(flows[k]), mk[k] = masks ? addr(masks[k]) : 0;
+    dis::PairMessage why;
+    DIS_ARG(dis::check_denoise_buffers(addr(cur), nb, fl, masks ? mk : nullptr, K, im.bytes, px * fsz, px, addr(dst),
+                                       px * channels, addr(support), dev ? fsz : 0, &why));
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // host frames are staged as they lie (rows and images keep their strides)
+    dis::HostStage st(s, !dev);
+    const uint8_t* dcur = st.in(cur, im.bytes);
+    const uint8_t* dnb[dis::kDenoiseMaxNeighbours];
+    const void* dfl[dis::kDenoiseMaxNeighbours];
+    const uint8_t* dmk[dis::kDenoiseMaxNeighbours];
+    for (int k = 0; k < K; ++k) {
+        dnb[k] = st.in(neighbours[k], im.bytes);
+        dfl[k] = st.in(flows[k], px * fsz);
+        dmk[k] = st.in(masks ? masks[k] : nullptr, px);
+    }
+    uint8_t* ddst = st.out(dst, px * channels);
+    uint8_t* dsup = st.out(support, px);
+    return st.finish([&] { return dis::launch_temporal_denoise(dcur, dnb, im.stride, im.image_stride, channels, dfl,
+                                                               flow_format == DIS_FLOW_F16, dmk, K, n, width, height,
+                                                               weights, ddst, dsup, s); }, "temporal denoising");
+}
+
 dis_status dis_flow_compose(const void* a, int a_format, const void* b, int b_format, int n, int width, int height,
                             const uint8_t* valid_a, const uint8_t* mask_b, void* out, int out_format,
                             uint8_t* valid_out, dis_mem where, void* stream, int device)

@@ -249,6 +249,19 @@ hipError_t launch_fit_motion(const void* flow, int f16, const uint8_t* mask, int
 // (out_f16 != 0) __half2 vectors; motion_flow_blocks(n, W, H) >= 1.
 hipError_t launch_motion_flow(const float* params, int n, int W, int H, void* out, int out_f16, hipStream_t s);
 
+// Motion-compensated temporal denoising of n W x H u8 images of `channels`
+// (1, 3, 4) interleaved samples (dis_denoise.hip, dis_temporal_denoise_u8): one
+// launch, a block per 64 x 16 pixels. `neighbours`, `flows` and `masks` are host
+// arrays of k_neighbours (1..8) device pointers, copied into the kernel's
+// arguments with the 256 host `weights`; masks or any of its entries and
+// support may be null. f16 != 0: the flows hold __half2 vectors (4-byte
+// aligned), else float2 (8-byte aligned). Strides in bytes, already resolved
+// (never 0). denoise_blocks(n, W, H) (dis_args.h) >= 1.
+hipError_t launch_temporal_denoise(const uint8_t* cur, const uint8_t* const* neighbours, size_t stride,
+                                   size_t image_stride, int channels, const void* const* flows, int f16,
+                                   const uint8_t* const* masks, int k_neighbours, int n, int W, int H,
+                                   const float* weights, uint8_t* dst, uint8_t* support, hipStream_t s, Timing t = {});
+
 // The init plane of a warm-started call (dis_init.hip): iw x ih = ceil(W_C / 2) x
 // ceil(H_C / 2) float2 per pair. launch_flow_to_init reduces n full-resolution
 // W x H flows to n planes (pad / clamp extension, C + 1 halvings, sanitising) in

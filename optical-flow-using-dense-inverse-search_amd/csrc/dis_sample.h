@@ -1,5 +1,5 @@
-// dis_sample.h -- the bilinear sampler of u8 images that dis_warp.hip and
-// dis_interp.hip share, and dis_interp.hip's loads of a lane's four flow
+// dis_sample.h -- the bilinear sampler of u8 images that dis_warp.hip,
+// dis_interp.hip and dis_denoise.hip share, and dis_interp.hip's loads of a lane's four flow
 // vectors (k_flow_warp keeps its own copy of those: calling load_flow4 there
 // changes its emitted code, calling warp_pixel from here does not).
 //

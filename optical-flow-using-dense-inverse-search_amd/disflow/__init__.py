@@ -114,6 +114,7 @@ EXPORTED_SYMBOLS = (
     "dis_flow_compose", "dis_flow_advect_points",
     "dis_flow_fill_workspace", "dis_flow_fill",
     "dis_flow_fit_motion_workspace", "dis_flow_fit_motion", "dis_motion_to_flow",
+    "dis_denoise_weights", "dis_temporal_denoise_u8",
 )
 
 
@@ -251,6 +252,9 @@ def lib() -> ctypes.CDLL:
             L.dis_flow_fit_motion_workspace.argtypes = [I, I, I, P(Z)]
             L.dis_flow_fit_motion.argtypes = [V, I, V, I, I, I, I, I, ctypes.c_float, V, V, V, V, I, V, I]
             L.dis_motion_to_flow.argtypes = [V, I, I, I, V, I, I, V, I]
+        if hasattr(L, "dis_temporal_denoise_u8"):
+            L.dis_denoise_weights.argtypes = [ctypes.c_float, V]
+            L.dis_temporal_denoise_u8.argtypes = [V, V, Z, Z, I, V, I, V, I, I, I, I, V, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -694,6 +698,120 @@ def motion_to_flow_device(params_ptr: int, n: int, width: int, height: int, out_
     _check(lib().dis_motion_to_flow(params_ptr, n, width, height, out_ptr, o_fmt, MEM_DEVICE, stream or None, device))
 
 
+DENOISE_MAX_NEIGHBOURS = 8
+
+
+def denoise_weights(sigma: float) -> np.ndarray:
+    """The Gaussian weight table of temporal_denoise (dis_denoise_weights, host
+    only): float32 (256,), table[d] = exp(-d^2 / (2 sigma^2)) computed in double
+    and rounded once; d is the mean absolute difference over a pixel's window."""
+    table = np.empty(256, np.float32)
+    _check(lib().dis_denoise_weights(float(sigma), _ptr(table)))
+    return table
+
+
+def _denoise_table(sigma, weights) -> np.ndarray:
+    if (sigma is None) == (weights is None):
+        raise ValueError("give exactly one of sigma and weights")
+    if weights is None:
+        return denoise_weights(sigma)
+    w = np.asarray(weights)
+    if w.dtype != np.float32 or w.shape != (256,):
+        raise ValueError(f"weights must be float32 (256,), not {w.dtype} {w.shape}")
+    return np.ascontiguousarray(w)
+
+
+def _pointer_array(ptrs, count: int, name: str, optional: bool = False):
+    """A host array of `count` pointers for the C-ABI (None / 0 entries are null)."""
+    ptrs = list(ptrs)
+    if len(ptrs) != count:
+        raise ValueError(f"{name} must have {count} entries, not {len(ptrs)}")
+    if not optional and any(not p for p in ptrs):
+        raise ValueError(f"{name} must not hold a null pointer")
+    return (ctypes.c_void_p * count)(*[int(p) if p else None for p in ptrs])
+
+
+def temporal_denoise(cur: np.ndarray, neighbours, flows, sigma=None, weights=None, masks=None,
+                     return_support: bool = False, device: int = 0):
+    """Motion-compensated temporal denoising (dis_temporal_denoise_u8) on the GPU:
+    each of the K (1..8) neighbours is warped to cur by its flow (flow_warp,
+    scale 1, "replicate") and blended in with weights[d], d the mean absolute
+    difference to cur over the pixel's 3 x 3 window and all channels:
+    out = cur + sum_k w_k (warped_k - cur) / (1 + sum_k w_k). cur and every
+    neighbour: u8 images of one shape, flow_warp's layouts; flows: K float32 or
+    float16 (..., H, W, 2) fields of one dtype and shape, cur -> neighbour k.
+    Give sigma (the table denoise_weights(sigma); about 1.5 times the noise's
+    standard deviation) or weights (float32 (256,) in [0, 1]). masks: None, or K
+    entries, each None or a u8 (..., H, W) plane whose zeros switch vectors off
+    (e.g. a consistency mask). Returns the denoised array in cur's shape;
+    return_support: also the u8 map (..., H, W) of how many neighbours took part."""
+    table = _denoise_table(sigma, weights)
+    img = np.asarray(cur)
+    nbs, fls = list(neighbours), list(flows)
+    K = len(nbs)
+    if not 1 <= K <= DENOISE_MAX_NEIGHBOURS:
+        raise ValueError(f"there must be 1 to {DENOISE_MAX_NEIGHBOURS} neighbours, not {K}")
+    if len(fls) != K or (masks is not None and len(masks) != K):
+        raise ValueError("neighbours, flows and masks must have one length")
+    fls = [np.asarray(f) for f in fls]
+    fl = fls[0]
+    fmt = _flow_format(fl.dtype)
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError("flows must be (H, W, 2) or (n, H, W, 2)")
+    if any(f.dtype != fl.dtype or f.shape != fl.shape for f in fls):
+        raise ValueError("flows must have one dtype and one shape")
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    if img.dtype != np.uint8:
+        raise ValueError(f"image dtype must be uint8, not {img.dtype}")
+    if img.ndim == 2:
+        shape4 = (1,) + img.shape + (1,)
+    elif img.ndim == 3:
+        shape4 = (1,) + img.shape if img.shape[:2] == (H, W) else img.shape + (1,)
+    elif img.ndim == 4:
+        shape4 = img.shape
+    else:
+        raise ValueError("images must be (H, W), (H, W, C), (n, H, W) or (n, H, W, C)")
+    if shape4[:3] != (n, H, W):
+        raise ValueError(f"image shape {img.shape} does not match flow shape {fl.shape}")
+    C = shape4[3]
+    if C not in (1, 3, 4):
+        raise ValueError(f"images must have 1, 3 or 4 channels, not {C}")
+    nbs = [np.asarray(a) for a in nbs]
+    if any(a.dtype != np.uint8 or a.shape != img.shape for a in nbs):
+        raise ValueError(f"every neighbour must be uint8 of cur's shape {img.shape}")
+    mks = [None] * K if masks is None else [None if m is None else _byte_plane(m, fl.shape[:-1], "mask") for m in masks]
+    img = np.ascontiguousarray(img)
+    nbs = [np.ascontiguousarray(a) for a in nbs]
+    fls = [np.ascontiguousarray(f) for f in fls]
+    out = np.empty(img.shape, np.uint8)
+    support = np.empty(fl.shape[:-1], np.uint8) if return_support else None
+    _check(lib().dis_temporal_denoise_u8(
+        _ptr(img), _pointer_array([_ptr(a) for a in nbs], K, "neighbours"), 0, 0, C,
+        _pointer_array([_ptr(f) for f in fls], K, "flows"), fmt,
+        None if masks is None else _pointer_array([None if m is None else _ptr(m) for m in mks], K, "masks", True),
+        K, n, W, H, _ptr(table), _ptr(out), _ptr(support) if return_support else None, MEM_HOST, None, device))
+    return (out, support) if return_support else out
+
+
+def temporal_denoise_device(cur_ptr: int, neighbour_ptrs, flow_ptrs, flow_dtype, n: int, width: int, height: int,
+                            channels: int, dst_ptr: int, sigma=None, weights=None, mask_ptrs=None, support_ptr: int = 0,
+                            stride: int = 0, image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_temporal_denoise_u8 on raw device pointers, asynchronous on `stream`:
+    neighbour_ptrs and flow_ptrs are sequences of K device pointers, mask_ptrs
+    None or K entries (0 / None: no mask for that neighbour); the weight table
+    (sigma or weights, as temporal_denoise's) is host memory."""
+    table = _denoise_table(sigma, weights)
+    fmt = _flow_format(flow_dtype)
+    neighbour_ptrs = list(neighbour_ptrs)
+    K = len(neighbour_ptrs)
+    nbs = _pointer_array(neighbour_ptrs, K, "neighbour_ptrs", True)  # (a null entry is the library's to refuse)
+    fls = _pointer_array(flow_ptrs, K, "flow_ptrs", True)
+    mks = None if mask_ptrs is None else _pointer_array(mask_ptrs, K, "mask_ptrs", True)
+    _check(lib().dis_temporal_denoise_u8(cur_ptr, nbs, stride, image_stride, channels, fls, fmt, mks, K, n, width, height,
+                                         _ptr(table), dst_ptr, support_ptr or None, MEM_DEVICE, stream or None, device))
+
+
 def advect_points(points: np.ndarray, flow: np.ndarray, with_status: bool = False, device: int = 0):
     """Points moved by flow fields (dis_flow_advect_points) on the GPU. flow:
     float32 or float16 (H, W, 2) with points (count, 2), or (n, H, W, 2) with
@@ -1045,6 +1163,36 @@ class DenseInverseSearch:
         ts = [_interp_time(t) for t in ts]  # raises before any device call
         fw, bw = self.calc_bidir(I0, I1)
         return [flow_interp(I0, I1, fw, t, bw=bw, return_fill=return_fill, device=self.device) for t in ts]
+
+    def denoise(self, frames, radius: int = 1, sigma: float = None, weights=None) -> np.ndarray:
+        """A sequence of T u8 frames (H x W; H x W x C on an engine with a colour
+        frame_format) denoised in time: for frame t the flows to the up to
+        2 * radius frames t - radius .. t + radius that exist (ascending, without
+        t; end frames have fewer) come from calc_batch, max_batch pairs a call
+        over the whole sequence, in the engine's flow_dtype as they are; then one
+        temporal_denoise(frame t, those frames, those flows, sigma or weights)
+        per frame, without masks. Returns the T denoised frames as one array; a
+        frame without a neighbour (T == 1) is returned as it is."""
+        table = _denoise_table(sigma, weights)  # raises before any device call
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or \
+                not 1 <= radius <= DENOISE_MAX_NEIGHBOURS // 2:
+            raise ValueError(f"radius must be an integer in [1, {DENOISE_MAX_NEIGHBOURS // 2}], not {radius!r}")
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        fr, _, T, _ = self._frames(fr, fr)
+        pairs = [(t, j) for t in range(T) for j in range(max(t - radius, 0), min(t + radius, T - 1) + 1) if j != t]
+        flows = []
+        for b in range(0, len(pairs), self.max_batch):
+            chunk = pairs[b:b + self.max_batch]
+            flows.extend(self.calc_batch(fr[[t for t, _ in chunk]], fr[[j for _, j in chunk]]))
+        out = np.empty_like(fr)
+        for t in range(T):
+            mine = [i for i, (a, _) in enumerate(pairs) if a == t]
+            if not mine:
+                out[t] = fr[t]
+                continue
+            out[t] = temporal_denoise(fr[t], [fr[pairs[i][1]] for i in mine], [flows[i] for i in mine],
+                                      weights=table, device=self.device)
+        return out
 
     def calc_bidir_device(self, n: int, I0_ptr: int, I1_ptr: int, fw_ptr: int, bw_ptr: int, stream: int = 0,
                           stride: int = 0, pair_stride: int = 0) -> None:
