@@ -205,6 +205,98 @@ def bilinear_replicate(I, X, Y):
     return ((f32(1) - fy) * top + fy * bot).astype(f32)
 
 
+def d5(f, axis):
+    """5-tap derivative (1, -8, 0, 8, -1) / 12 of a float32 plane along `axis`
+    (0: y, 1: x), replicate border."""
+    n = f.shape[axis]
+    i = np.arange(n)
+    a, b, c, d = (np.take(f, np.clip(i + k, 0, n - 1), axis=axis) for k in (-2, -1, 1, 2))
+    return ((((a - f32(8) * b) + f32(8) * c) - d) / f32(12)).astype(f32)
+
+
+VR_ALPHA, VR_GAMMA, VR_DELTA = f32(20), f32(10), f32(5)
+VR_ZETA, VR_EPS2, VR_OMEGA, VR_SOR_ITERS = f32(0.1), f32(1e-6), f32(1.6), 5
+
+
+def var_refine(I0, I1, flow, fp):
+    """Variational refinement of a (H, W, 2) flow between float32 level images
+    (the comment block above dis_oracle_var_refine in oracle/dis_oracle.c):
+    `fp` fixed-point iterations of warp, linearise, 5 red-black SOR sweeps
+    (omega 1.6, colour 0 = (x + y) even first), flow += increment. Whole planes
+    at a time; the SOR updates one colour under a boolean mask (a pixel's four
+    neighbours have the other colour, so the order within a colour is free)."""
+    I0 = np.ascontiguousarray(I0, f32)
+    I1 = np.ascontiguousarray(I1, f32)
+    flow = np.array(flow, f32, copy=True, order="C")
+    H, W = I0.shape
+    yy, xx = np.mgrid[0:H, 0:W]
+    xf, yf = xx.astype(f32), yy.astype(f32)
+    left, right, up, down = xx > 0, xx < W - 1, yy > 0, yy < H - 1
+    xl, xr = np.maximum(xx - 1, 0), np.minimum(xx + 1, W - 1)
+    yu, yd = np.maximum(yy - 1, 0), np.minimum(yy + 1, H - 1)
+    zero = np.zeros((H, W), f32)
+
+    def nb(p):
+        """p at the left / right / upper / lower neighbour (the pixel itself at a border)"""
+        return p[yy, xl], p[yy, xr], p[yu, xx], p[yd, xx]
+
+    I0x, I0y = d5(I0, 1), d5(I0, 0)
+    I0xx, I0xy, I0yy = d5(I0x, 1), d5(I0x, 0), d5(I0y, 0)
+    for _ in range(fp):
+        u, v = flow[..., 0].copy(), flow[..., 1].copy()
+        # 1. warp I1 by the current flow; derivatives of the pair
+        I1w = bilinear_replicate(I1, xf + u, yf + v)
+        Wx, Wy = d5(I1w, 1), d5(I1w, 0)
+        Ix = f32(0.5) * (Wx + I0x)
+        Iy = f32(0.5) * (Wy + I0y)
+        Iz = I1w - I0
+        Ixx = f32(0.5) * (d5(Wx, 1) + I0xx)
+        Ixy = f32(0.5) * (d5(Wx, 0) + I0xy)
+        Iyy = f32(0.5) * (d5(Wy, 0) + I0yy)
+        Ixz = Wx - I0x
+        Iyz = Wy - I0y
+        # 2. smoothness weight, forward differences (0 at the last column / row)
+        gxu = np.where(right, u[yy, xr] - u, zero)
+        gxv = np.where(right, v[yy, xr] - v, zero)
+        gyu = np.where(down, u[yd, xx] - u, zero)
+        gyv = np.where(down, v[yd, xx] - v, zero)
+        sw = (VR_ALPHA / np.sqrt((((gxu * gxu + gyu * gyu) + gxv * gxv) + gyv * gyv) + VR_EPS2)).astype(f32)
+        wl, wr = np.where(left, sw[yy, xl], zero), np.where(right, sw, zero)
+        wu, wd = np.where(up, sw[yu, xx], zero), np.where(down, sw, zero)
+        # 3. data weights and the normal equations of the linearised energy
+        psiI = VR_DELTA / np.sqrt(Iz * Iz + VR_EPS2)
+        psiG = VR_GAMMA / np.sqrt((Ixz * Ixz + Iyz * Iyz) + VR_EPS2)
+        A11 = (psiI * (Ix * Ix) + psiG * (Ixx * Ixx + Ixy * Ixy)) + VR_ZETA
+        A12 = psiI * (Ix * Iy) + psiG * (Ixx * Ixy + Ixy * Iyy)
+        A22 = (psiI * (Iy * Iy) + psiG * (Ixy * Ixy + Iyy * Iyy)) + VR_ZETA
+        ul, ur, uu, ud = nb(u)
+        vl, vr, vu, vd = nb(v)
+        su = ((wl * (ul - u) + wr * (ur - u)) + wu * (uu - u)) + wd * (ud - u)
+        sv = ((wl * (vl - v) + wr * (vr - v)) + wu * (vu - v)) + wd * (vd - v)
+        B1 = su - (psiI * (Iz * Ix) + psiG * (Ixz * Ixx + Iyz * Ixy))
+        B2 = sv - (psiI * (Iz * Iy) + psiG * (Ixz * Ixy + Iyz * Iyy))
+        sumw = ((wl + wr) + wu) + wd
+        D1, D2 = A11 + sumw, A22 + sumw
+        # 4. red-black SOR on the increment
+        du, dv = zero.copy(), zero.copy()
+        for _k in range(VR_SOR_ITERS):
+            for colour in (0, 1):
+                m = ((xx + yy) & 1) == colour
+                dl, dr, dup, ddn = nb(du)
+                sdu = ((wl * dl + wr * dr) + wu * dup) + wd * ddn
+                nu = (f32(1) - VR_OMEGA) * du + VR_OMEGA * (((B1 + sdu) - A12 * dv) / D1)
+                dl, dr, dup, ddn = nb(dv)
+                sdv = ((wl * dl + wr * dr) + wu * dup) + wd * ddn
+                nv = (f32(1) - VR_OMEGA) * dv + VR_OMEGA * (((B2 + sdv) - A12 * nu) / D2)
+                du[m] = nu[m]
+                dv[m] = nv[m]
+        # 5. flow += increment
+        flow[..., 0] = u + du
+        flow[..., 1] = v + dv
+    assert flow.dtype == f32
+    return flow
+
+
 def densify_paper(us, geom, I0, I1, W, H, ps, st):
     """Paper-mode densification: votes weighted by
     1 / max(1, |I1(x + u) - I0(x)|), patch-id order; I0/I1 unpadded level images."""
