@@ -478,6 +478,38 @@ inline void motionToFlow(const float* params, int n, int width, int height, half
     check(dis_motion_to_flow(params, n, width, height, out, DIS_FLOW_F16, where, stream, device));
 }
 
+// The corrections of a stabiliser (dis_motion_stabilize, host only): the
+// n_frames - 1 pair models of a video (fitMotion's params, frame k -> k+1; may
+// be null for one frame) composed into the camera path, the path smoothed by a
+// Gaussian of `sigma` frames cut at `radius` frames, and per frame the six
+// parameters that move it onto the smoothed path, magnified by `zoom` (1..16)
+// about the frame centre: what warpMotion takes. status (optional, n_frames
+// bytes): 0 where the smoothed path could not be inverted (that correction is all
+// zeros); replaced (optional): the pair models that were not finite and counted
+// as no motion.
+inline std::vector<float> stabilizePath(const float* pair_params, int n_frames, int width, int height, int radius,
+                                        float sigma, float zoom = 1.0f, uint8_t* status = nullptr,
+                                        int* replaced = nullptr)
+{
+    std::vector<float> corrections(n_frames > 0 ? (size_t)n_frames * 6 : 6);
+    check(dis_motion_stabilize(pair_params, n_frames, width, height, radius, sigma, zoom, corrections.data(), status,
+                               replaced));
+    return corrections;
+}
+
+// Backward warp (dis_warp_motion_u8) of n W x H u8 images of `channels` (1, 3, 4)
+// interleaved samples by n motion models of six parameters, on the GPU: bit for
+// bit motionToFlow followed by flowWarp at scale 1, without the field. params
+// lives where `where` says. valid (optional): 255 where the target lies inside
+// the frame.
+inline void warpMotion(const uint8_t* src, int channels, const float* params, int n, int width, int height,
+                       uint8_t* dst, Border border = Border::REPLICATE, uint8_t* valid = nullptr, size_t src_stride = 0,
+                       size_t src_image_stride = 0, dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_warp_motion_u8(src, src_stride, src_image_stride, channels, params, n, width, height,
+                             static_cast<int>(border), dst, valid, where, stream, device));
+}
+
 // Motion-compensated temporal denoising (dis_temporal_denoise_u8) of n W x H u8
 // images of `channels` (1, 3, 4) interleaved samples, on the GPU: each of the
 // k_neighbours (1..8) frames is warped to cur by its flow (cur -> neighbour k)

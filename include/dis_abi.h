@@ -770,6 +770,79 @@ dis_status dis_flow_fit_motion(const void* flow, int flow_format, const uint8_t*
 dis_status dis_motion_to_flow(const float* params, int n, int width, int height,
                               void* out, int out_format, dis_mem where, void* stream, int device);
 
+/* The camera path of a video smoothed, and per frame the model that steadies it
+ * (added within ABI v8, additive; host only, no GPU, like dis_denoise_weights):
+ * the stage between dis_flow_fit_motion and the warp of a stabiliser.
+ *   pair_params: (n_frames-1)*6 floats, entry k what dis_flow_fit_motion writes
+ *          for the flow from frame k to frame k+1 (may be NULL when n_frames is 1);
+ *   corrections: n_frames*6 floats, entry k the model q whose field warps frame
+ *          k into its stabilised version: it feeds dis_warp_motion_u8, or
+ *          dis_motion_to_flow and from there dis_flow_warp_u8;
+ *   status (may be NULL): n_frames bytes; replaced (may be NULL): one int.
+ * The result is defined by its arithmetic, all of it f64 with every operation
+ * rounded on its own and in the order stated. A matrix is 2 x 3 with an implied
+ * third row 0 0 1; a product a.b has the entries (a_i0*b_0j + a_i1*b_1j), with
+ * + a_i2 for j = 2, evaluated left to right.
+ * Pair matrices: A_k = [[1+p1, p2, p0], [p4, 1+p5, p3]], each p widened from
+ * f32; a model with any non-finite parameter is replaced by the identity, and
+ * *replaced counts those models.
+ * Path: C_0 = I, C_{k+1} = A_k . C_k.
+ * Weights: g(d) = (double)(float)exp(-((double)d*d) / (2.0*(double)sigma*
+ * (double)sigma)), dis_denoise_weights' rounding.
+ * Smoothed path, per entry: S_k = (sum_j g(|j-k|)*C_j) / (sum_j g(|j-k|)), j
+ * ascending over max(0, k-radius) .. min(n_frames-1, k+radius), both sums from
+ * +0.0.
+ * Inverse: det = s00*s11 - s01*s10; if det is not finite or |det| <= 2^-20,
+ * frame k's correction is six times +0.0f and status[k] = 0. Otherwise
+ * i00 = s11/det, i01 = -s01/det, i10 = -s10/det, i11 = s00/det,
+ * i02 = -(i00*s02 + i01*s12), i12 = -(i10*s02 + i11*s12).
+ * Correction: M_k = (C_k . S_k^-1) . Z with Z = [[z, 0, cx*(1-z)], [0, z,
+ * cy*(1-z)]], z = 1.0/(double)zoom, cx = (width-1)/2.0, cy = (height-1)/2.0
+ * (zoom > 1 magnifies about the centre, so that the moving borders leave the
+ * picture); q = (m02, m00-1, m01, m12, m10, m11-1), each value rounded once to
+ * f32, status[k] = 1; if any q is not finite the frame falls back to six times
+ * +0.0f and status 0.
+ * So identity pair models with zoom 1 give all-zero corrections bit for bit,
+ * radius 0 gives M = (C_k . C_k^-1) . Z (Z itself where that product is exact,
+ * as for translations), and n_frames = 1 is valid. Refused with
+ * DIS_ERR_INVALID_ARGUMENT: a null pair_params when n_frames > 1; a null
+ * corrections; n_frames < 1; width or height < 1 or > 2^24; radius outside
+ * 0..1024; a sigma that is not finite or not > 0; a zoom that is not finite or
+ * lies outside [1, 16]; any overlap of corrections, status or replaced with
+ * pair_params or each other. DIS_ERR_OUT_OF_MEMORY, with nothing written, when
+ * the 48 bytes of host memory a frame that the path needs cannot be had. */
+dis_status dis_motion_stabilize(const float* pair_params /* (n_frames-1)*6 */, int n_frames,
+                                int width, int height, int radius, float sigma, float zoom,
+                                float* corrections /* n_frames*6 */, uint8_t* status /* n_frames, may be NULL */,
+                                int* replaced /* may be NULL */);
+
+/* Backward warp of u8 images by motion models (added within ABI v8, additive; no
+ * context, like dis_flow_warp_u8; no reference counterpart): the stabilised
+ * frame straight from six numbers. For image i and pixel (x, y), with
+ * p = params + 6*i, in f32 with every operation rounded on its own:
+ *   u = (p0 + p1*(float)x) + p2*(float)y, v = (p3 + p4*(float)x) + p5*(float)y
+ * (dis_motion_to_flow's arithmetic exactly), then steps 1-5 of dis_flow_warp_u8
+ * at scale = 1. An image with any non-finite parameter gets every channel 0 and
+ * valid 0. dst and valid hold, bit for bit, what dis_motion_to_flow(DIS_FLOW_F32)
+ * followed by dis_flow_warp_u8 writes; no field exists anywhere.
+ *   src:   n images of W x H pixels of `channels` (1, 3 or 4) interleaved u8
+ *          samples, dis_flow_warp_u8's strides (0 = dense);
+ *   params: n*6 floats, where `where` says;
+ *   dst:   n dense W x H x channels images; valid (may be NULL): n W x H bytes.
+ * Refused with DIS_ERR_INVALID_ARGUMENT, before any device call: a null src,
+ * params or dst; n, width or height < 1; width or height > 2^24; channels other
+ * than 1, 3, 4; an unknown border or `where`; a stride smaller than a row or an
+ * image; more work than one launch's grid holds (a block per 64 x 16 pixels);
+ * any overlap of dst or valid with src, params or each other; for
+ * DIS_MEM_DEVICE params not 4-byte aligned. Image pointers need no alignment
+ * (aligned ones and W % 4 == 0 get wider accesses, same bytes). Host pointers:
+ * synchronous, staged through HIP device `device`; device pointers:
+ * asynchronous on `stream`, one launch, no allocation, no synchronisation. */
+dis_status dis_warp_motion_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                              const float* params /* n*6 */, int n, int width, int height, int border,
+                              uint8_t* dst, uint8_t* valid /* may be NULL */,
+                              dis_mem where, void* stream, int device);
+
 /* Motion-compensated temporal denoising of u8 images (added within ABI v8,
  * additive; no context, like dis_flow_warp_u8; no reference counterpart): each
  * of K neighbouring frames is warped to the current one by its flow and blended

@@ -58,7 +58,14 @@
 // the flow from it to that frame, which comes from the same engine in calls of
 // up to N pairs, with the table dis::denoiseWeights(SIGMA) and no masks; R in
 // [1, 4], SIGMA about 1.5 times the noise's standard deviation. Written as
-// OF_<folder>/frame_NNNN_denoised.png, 8-bit grey, colour with --color).
+// OF_<folder>/frame_NNNN_denoised.png, 8-bit grey, colour with --color),
+// --stabilize R (after the pairs: the pair models of the range -- --motion's
+// MODEL, similarity without it, fitted as above -- go through dis::stabilizePath
+// with radius R in [0, 1024], sigma max(R, 1) / 2 and --stab-zoom Z's zoom (1 by
+// default, up to 16), and every frame start .. end is warped by its correction
+// with dis::warpMotion, up to N frames a call. Written as
+// OF_<folder>/frame_NNNN_stab.png, 8-bit grey, colour with --color; the
+// corrections, one "%.9g" line per frame, as OF_<folder>/stab_corrections.txt).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -96,7 +103,8 @@ void usage()
                  "dis_flow folder start_num_image end_num_image max_iter patch_size coarsest_scale finest_scale "
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
-                 "--interp K  --color  --accumulate  --fill  --motion MODEL  --denoise R SIGMA"
+                 "--interp K  --color  --accumulate  --fill  --motion MODEL  --denoise R SIGMA  "
+                 "--stabilize R  --stab-zoom Z"
               << std::endl;
 }
 
@@ -126,6 +134,9 @@ int main(int argc, char** argv)
     int denoise = 0;     // --denoise: the radius R (0: off)
     float denoise_sigma = 0.0f;
     bool denoise_given = false;
+    int stabilize = 0;  // --stabilize: the radius R
+    bool stabilize_given = false;
+    float stab_zoom = 1.0f;
 
     std::vector<std::string> pos;
     for (int i = 1; i < argc; ++i) {
@@ -155,6 +166,11 @@ int main(int argc, char** argv)
             denoise = std::atoi(argv[++i]);
             denoise_sigma = (float)std::atof(argv[++i]);
             denoise_given = true;
+        } else if (a == "--stabilize" && i + 1 < argc) {
+            stabilize = std::atoi(argv[++i]);
+            stabilize_given = true;
+        } else if (a == "--stab-zoom" && i + 1 < argc) {
+            stab_zoom = (float)std::atof(argv[++i]);
         } else if (a == "--interp" && i + 1 < argc) {
             interp = std::atoi(argv[++i]);
         } else if (a == "--fb-alpha" && i + 2 < argc) {
@@ -199,6 +215,10 @@ int main(int argc, char** argv)
         std::cerr << "--denoise R SIGMA: R must lie in [1, 4] and SIGMA must be finite and > 0" << std::endl;
         return 2;
     }
+    if (stabilize_given && (stabilize < 0 || stabilize > 1024 || !(stab_zoom >= 1.0f && stab_zoom <= 16.0f))) {
+        std::cerr << "--stabilize R, --stab-zoom Z: R must lie in [0, 1024] and Z in [1, 16]" << std::endl;
+        return 2;
+    }
     if (warm_start && ((batch_given && batch > 1) || bidir)) {
         std::cerr << "--warm-start seeds each pair from the previous pair's flow: it cannot be combined with "
                   << (bidir ? "--bidir" : "--batch N > 1")
@@ -219,6 +239,7 @@ int main(int argc, char** argv)
         std::cerr << "--motion MODEL: MODEL must be translation, similarity or affine" << std::endl;
         return 2;
     }
+    if (stabilize_given && motion.empty()) motion_model = dis::MotionModel::SIMILARITY;
     struct stat sb;
     if (argc == 1 && ::stat(folder.c_str(), &sb) != 0) {  // no arguments and no default sequence here
         usage();
@@ -233,6 +254,7 @@ int main(int argc, char** argv)
         std::vector<float> prev_flow;  // --warm-start: the previous pair's flow (empty: start cold)
         std::vector<float> acc;        // --accumulate: the flow from frame `start` to the last pair's second frame
         std::vector<uint8_t> acc_valid;
+        std::vector<float> pair_models;  // --stabilize: the six parameters of every pair of the range
         for (int i0 = start; i0 < end; i0 += batch) {
             const int n = std::min(batch, end - i0);
             struct Frame {
@@ -301,11 +323,12 @@ int main(int argc, char** argv)
                               nullptr, device);
             }
             std::vector<float> motion_params;
-            if (!motion.empty()) {
+            if (!motion.empty() || stabilize_given) {
                 motion_params.resize((size_t)n * 6);
                 dis::fitMotion(flow.data(), n, W, H, motion_params.data(), motion_model, 3, 1.0f,
                                bidir ? mask.data() : nullptr, nullptr, nullptr, nullptr, DIS_MEM_HOST, nullptr, device);
             }
+            if (stabilize_given) pair_models.insert(pair_models.end(), motion_params.begin(), motion_params.end());
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             std::vector<uint8_t> warped, inside;
@@ -440,6 +463,49 @@ int main(int argc, char** argv)
                 else
                     png::write_gray(path, out.data(), W, H);
                 std::cout << "denoised " << frame_name(folder, start + t) << ".png from " << K << " frames" << std::endl;
+            }
+        }
+        if (stabilize_given && eng) {  // --stabilize: every frame of the range onto the smoothed camera path
+            const int C = color ? 3 : 1, T = end - start + 1;
+            const size_t fsz = (size_t)W * H * C;
+            if (pair_models.size() != (size_t)(T - 1) * 6)
+                throw std::runtime_error("--stabilize: the frame size changed within the range");
+            const std::vector<float> corr =
+                dis::stabilizePath(pair_models.data(), T, W, H, stabilize, (float)std::max(stabilize, 1) / 2.0f, stab_zoom);
+            std::FILE* cf = std::fopen((out_dir + "/stab_corrections.txt").c_str(), "w");
+            if (!cf) throw std::runtime_error("cannot write " + out_dir + "/stab_corrections.txt");
+            for (int t = 0; t < T; ++t) {
+                const float* m = corr.data() + (size_t)t * 6;
+                std::fprintf(cf, "%.9g %.9g %.9g %.9g %.9g %.9g\n", m[0], m[1], m[2], m[3], m[4], m[5]);
+            }
+            if (std::fclose(cf) != 0) throw std::runtime_error("cannot write " + out_dir + "/stab_corrections.txt");
+            for (int t0 = 0; t0 < T; t0 += batch) {
+                const int n = std::min(batch, T - t0);
+                std::vector<uint8_t> src((size_t)n * fsz), dst((size_t)n * fsz);
+                for (int k = 0; k < n; ++k) {
+                    const std::string path = frame_name(folder, start + t0 + k) + ".png";
+                    int w, h;
+                    std::vector<uint8_t> px;
+                    if (color) {
+                        png::Rgb f = png::read_rgb(path);
+                        w = f.width, h = f.height, px = std::move(f.px);
+                    } else {
+                        png::Gray f = png::read_gray(path);
+                        w = f.width, h = f.height, px = std::move(f.px);
+                    }
+                    if (w != W || h != H) throw std::runtime_error("--stabilize: frame sizes differ within the range");
+                    std::copy(px.begin(), px.end(), src.begin() + (size_t)k * fsz);
+                }
+                dis::warpMotion(src.data(), C, corr.data() + (size_t)t0 * 6, n, W, H, dst.data(), dis::Border::REPLICATE,
+                                nullptr, 0, 0, DIS_MEM_HOST, nullptr, device);
+                for (int k = 0; k < n; ++k) {
+                    const std::string path = "OF_" + frame_name(folder, start + t0 + k) + "_stab.png";
+                    if (color)
+                        png::write_rgb(path, dst.data() + (size_t)k * fsz, W, H);
+                    else
+                        png::write_gray(path, dst.data() + (size_t)k * fsz, W, H);
+                    std::cout << "stabilised " << frame_name(folder, start + t0 + k) << ".png" << std::endl;
+                }
             }
         }
     } catch (const std::exception& e) {

@@ -316,4 +316,66 @@ inline const char* check_denoise_buffers(uintptr_t cur, const uintptr_t* neighbo
     return check_disjoint(r, nin, m, why);
 }
 
+// dis_warp_motion_u8: a block per 64 x 16 output pixels and image (a lane per 4
+// pixels of a row). Blocks of the launch over n images; -1 when they exceed a
+// grid (which also keeps every byte count of the call far below 2^63).
+constexpr int kWarpMotionTileW = 64, kWarpMotionTileH = 16;
+inline long long warp_motion_blocks(int n, int width, int height)
+{
+    const long long tx = ((long long)width + kWarpMotionTileW - 1) / kWarpMotionTileW;
+    const long long ty = ((long long)height + kWarpMotionTileH - 1) / kWarpMotionTileH;
+    if (n < 1 || tx < 1 || ty < 1 || tx * ty > 0x7fffffffLL / n) return -1;
+    return tx * ty * n;
+}
+
+// The sizes of dis_warp_motion_u8: the sides, the channels and the grid.
+inline const char* check_warp_motion_sizes(int n, int width, int height, int channels)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide)) return why;
+    if (channels != 1 && channels != 3 && channels != 4) return "channels must be 1, 3 or 4";
+    if (warp_motion_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    return nullptr;
+}
+
+// The buffers of dis_warp_motion_u8 by address: src (image_bytes) and params
+// (24 bytes an image) are read, dst and valid (pixels bytes, 0 = absent)
+// written. params_align: 4 for device pointers, else 0.
+inline const char* check_warp_motion_buffers(uintptr_t src, size_t image_bytes, uintptr_t params, int n, uintptr_t dst,
+                                             size_t dst_bytes, uintptr_t valid, size_t pixels, size_t params_align,
+                                             PairMessage* why)
+{
+    if (params_align && (params & (params_align - 1))) return "params must be 4-byte aligned";
+    const NamedRange r[4] = {{src, image_bytes, "src"}, {params, (size_t)24 * (size_t)n, "params"},
+                             {dst, dst_bytes, "dst"}, {valid, valid ? pixels : 0, "valid"}};
+    return check_disjoint(r, 2, 4, why);
+}
+
+// dis_motion_stabilize: the values (a float compares false with everything
+// when it is NaN, so each test is written to fail for one) ...
+constexpr int kMaxStabilizeRadius = 1024;
+inline const char* check_stabilize(int n_frames, int width, int height, int radius, float sigma, float zoom)
+{
+    if (n_frames < 1) return "n_frames must be >= 1";
+    if (width < 1 || height < 1) return "width and height must be >= 1";
+    if (width > kMaxExactSide || height > kMaxExactSide) return "width or height too large";
+    if (radius < 0 || radius > kMaxStabilizeRadius) return "radius must be in [0, 1024]";
+    if (!(sigma > 0.0f && sigma <= 3.40282347e38f)) return "sigma must be finite and > 0";
+    if (!(zoom >= 1.0f && zoom <= 16.0f)) return "zoom must be finite and in [1, 16]";
+    return nullptr;
+}
+
+// ... and the buffers by address: pair_params ((n_frames - 1) * 24 bytes) is
+// read; corrections (n_frames * 24), status (n_frames, 0 = absent) and
+// replaced (one int, 0 = absent) are written.
+inline const char* check_stabilize_buffers(uintptr_t pair_params, uintptr_t corrections, uintptr_t status,
+                                           uintptr_t replaced, int n_frames, PairMessage* why)
+{
+    const size_t n = (size_t)n_frames;
+    const NamedRange r[4] = {{pair_params, pair_params ? (n - 1) * 24 : 0, "pair_params"},
+                             {corrections, n * 24, "corrections"},
+                             {status, status ? n : 0, "status"},
+                             {replaced, replaced ? sizeof(int) : 0, "replaced"}};
+    return check_disjoint(r, 1, 4, why);
+}
+
 }  // namespace dis

@@ -356,6 +356,35 @@ dis_status dis_motion_to_flow(const float* params, int n, int width, int height,
                      "motion field");
 }
 
+dis_status dis_warp_motion_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                              const float* params, int n, int width, int height, int border, uint8_t* dst, uint8_t* valid,
+                              dis_mem where, void* stream, int device)
+{
+    if (!src || !params || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_warp_motion_sizes(n, width, height, channels));  // sizes, channels and the grid
+    if (border != DIS_BORDER_REPLICATE && border != DIS_BORDER_ZERO)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "border must be DIS_BORDER_REPLICATE or DIS_BORDER_ZERO");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    dis::ImageStack im;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, src_stride, src_image_stride, &im));
+    const bool dev = where == DIS_MEM_DEVICE;
+    const size_t px = (size_t)width * height * n;
+    dis::PairMessage why;
+    DIS_ARG(dis::check_warp_motion_buffers(addr(src), im.bytes, addr(params), n, addr(dst), px * channels, addr(valid), px,
+                                           dev ? 4 : 0, &why));
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int zero = border == DIS_BORDER_ZERO;
+    // a host source is staged as it lies (rows and images keep their strides)
+    dis::HostStage st(s, !dev);
+    const uint8_t* dsrc = st.in(src, im.bytes);
+    const float* dparams = st.in(params, sizeof(float) * 6 * n);
+    uint8_t* ddst = st.out(dst, px * channels);
+    uint8_t* dvalid = st.out(valid, px);
+    return st.finish([&] { return dis::launch_warp_motion(dsrc, im.stride, im.image_stride, channels, dparams, n, width,
+                                                          height, zero, ddst, dvalid, s); }, "motion warp");
+}
+
 dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int width, int height, const float* points,
                                   int count, float* points_out, uint8_t* status, dis_mem where, void* stream, int device)
 {

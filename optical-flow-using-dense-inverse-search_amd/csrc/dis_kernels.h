@@ -249,6 +249,21 @@ hipError_t launch_fit_motion(const void* flow, int f16, const uint8_t* mask, int
 // (out_f16 != 0) __half2 vectors; motion_flow_blocks(n, W, H) >= 1.
 hipError_t launch_motion_flow(const float* params, int n, int W, int H, void* out, int out_f16, hipStream_t s);
 
+// Backward warp of n W x H u8 images of `channels` (1, 3, 4) interleaved samples
+// by n motion models of six device floats each (dis_warpmotion.hip,
+// dis_warp_motion_u8): launch_motion_flow's vectors computed in registers, then
+// launch_flow_warp's pixel at scale 1; one launch, a block per 64 x 16 pixels;
+// with 3 channels the taps come from an LDS image of the tile's source box
+// where it fits. valid may be null. Strides in bytes, already resolved (never
+// 0). warp_motion_blocks(n, W, H) (dis_args.h) >= 1. direct_only != 0: the
+// kernel without the LDS route (the same bytes; for A/B timing). routes
+// (null in the library's own calls): three device counters the launch adds to --
+// blocks that staged their box, blocks that ran the direct form, pixels of
+// staged blocks that read global memory -- for tools/stabilize_ab's route mode.
+hipError_t launch_warp_motion(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                              const float* params, int n, int W, int H, int zero_border, uint8_t* dst, uint8_t* valid,
+                              hipStream_t s, Timing t = {}, int direct_only = 0, unsigned* routes = nullptr);
+
 // Motion-compensated temporal denoising of n W x H u8 images of `channels`
 // (1, 3, 4) interleaved samples (dis_denoise.hip, dis_temporal_denoise_u8): one
 // launch, a block per 64 x 16 pixels. `neighbours`, `flows` and `masks` are host

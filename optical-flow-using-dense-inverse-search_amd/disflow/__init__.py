@@ -115,6 +115,7 @@ EXPORTED_SYMBOLS = (
     "dis_flow_fill_workspace", "dis_flow_fill",
     "dis_flow_fit_motion_workspace", "dis_flow_fit_motion", "dis_motion_to_flow",
     "dis_denoise_weights", "dis_temporal_denoise_u8",
+    "dis_motion_stabilize", "dis_warp_motion_u8",
 )
 
 
@@ -255,6 +256,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_temporal_denoise_u8"):
             L.dis_denoise_weights.argtypes = [ctypes.c_float, V]
             L.dis_temporal_denoise_u8.argtypes = [V, V, Z, Z, I, V, I, V, I, I, I, I, V, V, V, I, V, I]
+        if hasattr(L, "dis_warp_motion_u8"):  # (added within v8)
+            L.dis_motion_stabilize.argtypes = [V, I, I, I, I, ctypes.c_float, ctypes.c_float, V, V, P(I)]
+            L.dis_warp_motion_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, V, V, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -696,6 +700,110 @@ def motion_to_flow_device(params_ptr: int, n: int, width: int, height: int, out_
     """dis_motion_to_flow on raw device pointers, asynchronous on `stream`."""
     o_fmt = _flow_format(out_dtype)
     _check(lib().dis_motion_to_flow(params_ptr, n, width, height, out_ptr, o_fmt, MEM_DEVICE, stream or None, device))
+
+
+STABILIZE_MAX_RADIUS = 1024
+
+
+def _stabilize_args(radius, sigma, zoom):
+    """(radius, sigma, zoom) of stabilize_path, checked as the library checks them;
+    sigma None: max(radius, 1) / 2."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or \
+            not 0 <= radius <= STABILIZE_MAX_RADIUS:
+        raise ValueError(f"radius must be an integer in [0, {STABILIZE_MAX_RADIUS}], not {radius!r}")
+    s = max(int(radius), 1) / 2.0 if sigma is None else float(sigma)
+    if not (0.0 < s <= float(np.finfo(np.float32).max)) or float(np.float32(s)) <= 0.0:  # (false for NaN)
+        raise ValueError(f"sigma must be finite and > 0, not {sigma!r}")
+    z = float(zoom)
+    if not 1.0 <= z <= 16.0:  # (false for NaN)
+        raise ValueError(f"zoom must lie in [1, 16], not {zoom!r}")
+    return int(radius), s, z
+
+
+def stabilize_path(pair_params, width: int, height: int, radius: int, sigma=None, zoom: float = 1.0,
+                   with_status: bool = False):
+    """The corrections of a stabiliser (dis_motion_stabilize, host only): the
+    float32 (N-1, 6) models of consecutive pairs (fit_motion's params, frame k ->
+    k+1; shape (0, 6) for a single frame) are composed into the camera path, the
+    path is smoothed by a Gaussian of `sigma` frames (None: max(radius, 1) / 2)
+    cut at `radius` frames, and frame k's correction is the model that moves it
+    from the path onto the smoothed path, magnified by `zoom` (1..16) about the
+    centre of the W x H frame. Returns float32 (N, 6): what warp_motion takes
+    (or motion_to_flow and flow_warp). A pair model that is not finite (a failed
+    fit) counts as no motion. with_status: (corrections, status u8 (N,),
+    replaced): status 0 where the smoothed path could not be inverted (the
+    correction is then all zeros), replaced the number of pair models that
+    were not finite."""
+    r, s, z = _stabilize_args(radius, sigma, zoom)
+    p = np.asarray(pair_params)
+    if p.dtype != np.float32:
+        raise ValueError(f"pair_params dtype must be float32, not {p.dtype}")
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError(f"pair_params must be (N-1, 6), not {p.shape}")
+    if isinstance(width, bool) or isinstance(height, bool) or not isinstance(width, (int, np.integer)) or \
+            not isinstance(height, (int, np.integer)) or width < 1 or height < 1:
+        raise ValueError(f"width and height must be integers >= 1, not {width!r}, {height!r}")
+    p = np.ascontiguousarray(p)
+    n = p.shape[0] + 1
+    out = np.empty((n, 6), np.float32)
+    status = np.empty(n, np.uint8)
+    replaced = ctypes.c_int(0)
+    _check(lib().dis_motion_stabilize(_ptr(p) if n > 1 else None, n, int(width), int(height), r, s, z, _ptr(out),
+                                      _ptr(status), ctypes.byref(replaced)))
+    return (out, status, int(replaced.value)) if with_status else out
+
+
+def warp_motion(image: np.ndarray, params: np.ndarray, border="replicate", return_valid: bool = False,
+                device: int = 0):
+    """Backward warp (dis_warp_motion_u8) of u8 images by motion models on the
+    GPU: bit for bit flow_warp(image, motion_to_flow(params, W, H)), without the
+    field. image: (H, W) or (H, W, C) with params float32 (6,), or (n, H, W) or
+    (n, H, W, C) with params (n, 6); C in 1, 3, 4. border: "replicate" or "zero".
+    Returns the warped array of the image's shape; return_valid: also the u8 mask
+    (..., H, W), 255 where the target lies inside the frame. A model with a
+    parameter that is not finite gives 0 everywhere and valid 0."""
+    bd = _border(border)
+    img = np.asarray(image)
+    if img.dtype != np.uint8:
+        raise ValueError(f"image dtype must be uint8, not {img.dtype}")
+    p = np.asarray(params)
+    if p.dtype != np.float32:
+        raise ValueError(f"params dtype must be float32, not {p.dtype}")
+    if p.ndim not in (1, 2) or p.shape[-1] != 6 or p.size == 0:
+        raise ValueError(f"params must be (6,) or (n, 6), not {p.shape}")
+    if p.ndim == 1:
+        if img.ndim not in (2, 3):
+            raise ValueError("one model takes an (H, W) or (H, W, C) image")
+        shape4 = (1,) + img.shape + ((1,) if img.ndim == 2 else ())
+    else:
+        if img.ndim not in (3, 4):
+            raise ValueError("(n, 6) models take (n, H, W) or (n, H, W, C) images")
+        shape4 = img.shape + ((1,) if img.ndim == 3 else ())
+        if shape4[0] != p.shape[0]:
+            raise ValueError(f"image shape {img.shape} does not match params shape {p.shape}")
+    n, H, W, C = shape4
+    if C not in (1, 3, 4):
+        raise ValueError(f"image must have 1, 3 or 4 channels, not {C}")
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"image shape {img.shape} has an empty dimension")
+    img = np.ascontiguousarray(img)
+    p = np.ascontiguousarray(p)
+    out = np.empty(img.shape, np.uint8)
+    valid = np.empty(shape4[:3] if p.ndim == 2 else shape4[1:3], np.uint8) if return_valid else None
+    _check(lib().dis_warp_motion_u8(_ptr(img), 0, 0, C, _ptr(p), n, W, H, bd, _ptr(out),
+                                    _ptr(valid) if return_valid else None, MEM_HOST, None, device))
+    return (out, valid) if return_valid else out
+
+
+def warp_motion_device(src_ptr: int, params_ptr: int, n: int, width: int, height: int, channels: int, dst_ptr: int,
+                       valid_ptr: int = 0, border="replicate", src_stride: int = 0, src_image_stride: int = 0,
+                       stream: int = 0, device: int = 0) -> None:
+    """dis_warp_motion_u8 on raw device pointers (params_ptr: n * 6 float32 in
+    device memory), asynchronous on `stream`: one launch, no allocation, no
+    synchronisation."""
+    bd = _border(border)
+    _check(lib().dis_warp_motion_u8(src_ptr, src_stride, src_image_stride, channels, params_ptr, n, width, height, bd,
+                                    dst_ptr, valid_ptr or None, MEM_DEVICE, stream or None, device))
 
 
 DENOISE_MAX_NEIGHBOURS = 8
@@ -1193,6 +1301,50 @@ class DenseInverseSearch:
             out[t] = temporal_denoise(fr[t], [fr[pairs[i][1]] for i in mine], [flows[i] for i in mine],
                                       weights=table, device=self.device)
         return out
+
+    def stabilize(self, frames, model="similarity", radius: int = 15, sigma=None, zoom: float = 1.0,
+                  iterations: int = 3, threshold: float = 1.0, border="replicate", return_models: bool = False):
+        """A sequence of N u8 frames (H x W; H x W x C on an engine with a colour
+        frame_format) steadied: the flows of the N - 1 consecutive pairs (calc on
+        device buffers, max_batch pairs a call, in the engine's flow_dtype as they
+        are), fit_motion(model, iterations, threshold) of each on the device,
+        stabilize_path(radius, sigma, zoom) of the (N - 1, 6) models on the host
+        -- the only numbers that leave the device before the result -- and one
+        warp_motion(border) of the frames as given by the corrections. Returns
+        the N stabilised frames as one array; return_models: (frames, pair models
+        (N - 1, 6), corrections (N, 6)). The device buffers are torch tensors on
+        the engine's device, on the null stream."""
+        mdl, its, thr = _motion_args(model, iterations, threshold)  # all raise before any device call
+        _stabilize_args(radius, sigma, zoom)
+        bd = _border(border)
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        fr, _, N, row = self._frames(fr, fr)
+        import torch
+
+        W, H, C = self.width, self.height, self._frame_channels
+        dev = torch.device("cuda", self.device)
+        dfr = torch.from_numpy(fr if fr.flags.writeable else fr.copy()).to(dev)  # (torch wants a writable source)
+        pair = np.empty((N - 1, 6), np.float32)
+        if N > 1:
+            nb = min(self.max_batch, N - 1)
+            dflow = torch.empty((nb, H, W, 2), dtype=torch.float16 if self.flow_dtype == np.float16 else torch.float32,
+                                device=dev)
+            dpar = torch.empty((N - 1, 6), dtype=torch.float32, device=dev)
+            dws = torch.empty(fit_motion_workspace(nb, W, H) // 8, dtype=torch.float64, device=dev)
+            for k in range(0, N - 1, nb):
+                b = min(nb, N - 1 - k)
+                self.calc_device(b, dfr[k].data_ptr(), dfr[k + 1].data_ptr(), dflow.data_ptr(), stride=row,
+                                 pair_stride=row * H)
+                fit_motion_device(dflow.data_ptr(), self.flow_dtype, b, W, H, dpar[k].data_ptr(), dws.data_ptr(),
+                                  model=mdl, iterations=its, threshold=thr, device=self.device)
+            pair = dpar.cpu().numpy()
+        corr = stabilize_path(pair, W, H, radius, sigma, zoom)
+        dcorr = torch.from_numpy(corr).to(dev)
+        dout = torch.empty_like(dfr)
+        warp_motion_device(dfr.data_ptr(), dcorr.data_ptr(), N, W, H, C, dout.data_ptr(), border=bd,
+                           device=self.device)
+        out = dout.cpu().numpy()
+        return (out, pair, corr) if return_models else out
 
     def calc_bidir_device(self, n: int, I0_ptr: int, I1_ptr: int, fw_ptr: int, bw_ptr: int, stream: int = 0,
                           stride: int = 0, pair_stride: int = 0) -> None:
