@@ -39,7 +39,12 @@ CASES = [
     Case("synth-dense",  ("synth", 50),                96, 80, 3, 1, 0.8,    1, 2),    # steps 1; densify + upsample back end
     Case("synth-vr",     ("synth", 60),                160, 120, 3, 1, 0.625, 1, 3, batch=2, vr=2),
     Case("synth-warm",   ("synth", 21),                128, 96, 2, 1, 0.5,   1, 3, warm=True),
+    # grid steps 5, 6, 7 (overlaps exact in binary): tile strides 72 / 66 / 72 at 2 and 8 lanes per patch
+    Case("shift-step5",  ("shift", 7, 1.3, -0.8),      104, 72, 2, 0, 0.375, 1, 3),    # steps 5
+    Case("scene-step6",  ("scene", 33),                160, 120, 3, 1, 0.25, 1, 3),    # steps 6
+    Case("synth-step7",  ("synth", 7),                 136, 104, 3, 0, 0.125, 1, 3),   # steps 7
 ]
+STEPS = {"shift-step5": 5, "scene-step6": 6, "synth-step7": 7}  # the grid step a case is there for (asserted)
 BY_NAME = {c.name: c for c in CASES}
 
 _cache = {}
@@ -94,8 +99,58 @@ def warm_plane(case):
     return _once(("warm", case.name), make)
 
 
+# tile_layout of dis_search8.hip per grid step, as the table in tests/test_gpu_fma_levels.py
+# states it: (LPP 1 stride or None where LPP 1 does not fit and runs as LPP 2, LPP 2 stride,
+# LPP 2 half-wave layout (0: 2 x 8, 1: 4 x 4 patches), LPP 4 stride, LPP 8 stride)
+TILE_TABLE = {
+    1: (100, 72, 1, 68, 72),
+    2: (98, 66, 0, 66, 68),
+    3: (100, 72, 1, 68, 72),
+    4: (97, 65, 0, 65, 66),
+    5: (100, 72, 1, 68, 72),
+    6: (98, 66, 0, 66, 68),
+    7: (100, 72, 1, 68, 72),
+    8: (None, 65, 0, 65, 65),
+}
+LAUNCH_TS_STRIDES = (65, 66, 68, 72)  # the strides launch_ts holds as template constants
+
+
+def tile_layout(st, lpp):
+    """tile_bank_multiplicity / tile_layout of dis_search8.hip restated (not read from the
+    library, which exports neither): the LDS tile row stride in (tile width, max stride]
+    and, at 2 lanes per patch, the half-wave layout with the least worst-case bank
+    multiplicity of a 32-lane group's reads at zero flow; ties keep the first candidate."""
+    w, smax = (96, 128) if lpp == 1 else (64, 72)
+
+    def multiplicity(quad, S):
+        cnt = [0] * 32
+        for l in range(32):
+            if lpp == 1:
+                gx, gy, off = l >> 3, l & 7, 0
+            elif lpp == 2:
+                p = l >> 1
+                gx, gy, off = ((p & 3), (p >> 2) & 3, 4 * (l & 1)) if quad else (p >> 3, p & 7, 4 * (l & 1))
+            elif lpp == 4:
+                gx, gy, off = 0, l >> 2, l & 3
+            else:
+                gx, gy, off = 0, (l >> 4) * 2 + ((l >> 2) & 1), (l & 3) | (((l >> 3) & 1) << 2)
+            cnt[(st * S * gy + st * gx + off) % 32] += 1
+        return max(cnt)
+
+    best = min(((multiplicity(q, S), q, S) for q in range(2 if lpp == 2 else 1) for S in range(w + 1, smax + 1)),
+               key=lambda t: t[0])  # min keeps the first of equals: quad 0 before 1, strides ascending
+    return best[2], best[1]
+
+
+def lpp1_fits(st):
+    """search8_lpp1_fits: the 16 x 8 block's I0 region in the 64 x 128 tile buffer."""
+    return (15 * st + 11) * (7 * st + 10) <= 64 * 128
+
+
 def steps(case):
-    return ob.steps(PS, case.ov)
+    st = ob.steps(PS, case.ov)
+    assert st == STEPS.get(case.name, st), (case.name, st)
+    return st
 
 
 def pyramids(case, k):

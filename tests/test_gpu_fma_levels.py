@@ -31,23 +31,33 @@ every case and lane layout:
 
 Which kernel a case reaches (patch size 8; tile_layout of dis_search8.hip
 restated: grid step -> LDS tile stride per lanes-per-patch layout, and the
-LPP-2 half-wave layout):
+LPP-2 half-wave layout). Restated, not read from the library, which exports
+neither search8_tile_stride nor search8_tile_quad: fma_cases.tile_layout is
+the restatement, fma_cases.TILE_TABLE this table, and
+tests/test_search64_host.py holds the two together on the CPU.
 
     steps (overlap)      LPP 1   LPP 2        LPP 4   LPP 8
     1 (0.8)              100     72 (4 x 4)   68      72
     2 (0.75)             98      66 (2 x 8)   66      68
     3 (0.625)            100     72 (4 x 4)   68      72
     4 (0.5)              97      65 (2 x 8)   65      66
+    5 (0.375)            100     72 (4 x 4)   68      72
+    6 (0.25)             98      66 (2 x 8)   66      68
+    7 (0.125)            100     72 (4 x 4)   68      72
     8 (0.0)              LPP 2   65 (2 x 8)   65      65
 
 Variants 3 / 2 / 4 / 5 force 2 / 4 / 8 / 1 lanes per patch, 9 is LPP 2 with
 most blocks through the fallback list (k_search8_fb<2, kFma>), 0 picks per
-level (8 lanes here: every level is below kLpp8MaxPatches). Together this is
-every kFma instantiation launch_search8_t<false, true> can launch: launch_ts
-only specialises LPP 2 and 8, over strides 65 / 66 / 68 / 72, and its
-run-time-stride default is unreachable at patch size 8. Paper mode, other
-patch sizes and the wave-per-patch kernel always run the exact kernels and
-are bit-exact elsewhere.
+level (8 lanes here: every level is below kLpp8MaxPatches). These are all
+eight grid steps patch size 8 can have, so together this is every kFma
+instantiation launch_search8_t<false, true> can launch, each at every step
+that reaches it: launch_ts only specialises LPP 2 and 8, over strides 65 /
+66 / 68 / 72, which are the only strides the table gives those two layouts
+at any step, so its run-time-stride default is unreachable at patch size 8
+(steps 5 to 7 reach the 72, 66 / 68 and 72 instantiations that steps 1 to 3
+reach, at wider I0 regions). Paper mode, other patch sizes and the
+wave-per-patch kernel always run the exact kernels and are bit-exact
+elsewhere (tests/test_gpu_parity.py, tests/test_gpu_grid_steps.py).
 """
 import numpy as np
 import pytest
@@ -60,7 +70,7 @@ import searchref64 as s64
 pytestmark = pytest.mark.gpu
 
 VARIANTS = {0: "auto", 3: "LPP2", 2: "LPP4", 4: "LPP8", 5: "LPP1", 9: "LPP2-fallback"}
-FALLBACK_CASES = ("shift-it0", "shift-it3", "bigshift", "scene31")
+FALLBACK_CASES = ("shift-it0", "shift-it3", "bigshift", "scene31", "shift-step5")
 PARAMS = [(c, v) for c in fc.CASES for v in VARIANTS if v != 9 or c.name in FALLBACK_CASES]
 MEDIAN_RHO_SANITY = 10.0  # tests/test_search64_host.py
 

@@ -70,6 +70,22 @@ def test_grid_geometry_medium_1080p(oracle):
     assert sum(counts) == 77700
 
 
+def test_step_equal_to_patch_size_tiles_every_level(oracle):
+    # overlap 0: the grid has ceil(w / ps) patches and is centred (src/patch_grid.cpp:27-37),
+    # r = w - (npw - 1) ps in [1, ps] and the first reference point sits at r // 2, so the
+    # footprints [ref - ps/2, ref + ps/2) start at or before pixel 0 and end at or after
+    # pixel w - 1 (ceil(r / 2) <= ps / 2): every pixel of every level is covered by exactly
+    # one patch and the densification's w == 0 branch cannot run with an overlap in [0, 1)
+    for ps in range(2, 17, 2):
+        assert oracle.steps(ps, 0.0) == ps
+        for w in range(1, 200):
+            npw, _, offw, _ = oracle.grid(w, 8, ps)
+            n = np.zeros(w, int)
+            for g in range(npw):
+                n[max(g * ps + offw - ps // 2, 0):min(g * ps + offw + ps // 2, w)] += 1
+            assert (n == 1).all(), (ps, w, npw, offw)
+
+
 def test_padding_split(oracle):
     assert oracle.padded_size(1920, 1080, 6) == (1920, 1088, 0, 4)
     assert oracle.padded_size(641, 483, 3) == (648, 488, 3, 2)
@@ -104,9 +120,25 @@ def test_level0_is_sobel_magnitude(oracle):
     assert np.array_equal(lv0, np.sqrt(gx * gx + gy * gy))
 
 
+# (patch size, overlap) -> the grid step a row of the two oracle <-> numpy tests
+# below is there for: every step of patch size 8, step 1 and step = ps of generic
+# sizes, patch sizes 12 and 14. The tests assert it, so a change of the overlap
+# constants cannot silently move a row to another step.
+ROW_STEP = {(8, 0.625): 3, (8, 0.7): 2, (4, 0.5): 2, (6, 0.5): 3,
+            (8, 0.875): 1, (8, 0.375): 5, (8, 0.25): 6, (8, 0.125): 7, (8, 0.0): 8,
+            (12, 0.25): 9, (12, 0.0): 12, (14, 0.5): 7, (16, 0.9375): 1, (16, 0.0): 16,
+            (2, 0.5): 1, (10, 0.05): 9}
+
+
 @pytest.mark.parametrize("ps,overlap,it,norm", [(8, 0.625, 4, 1), (4, 0.5, 3, 1), (6, 0.5, 2, 0),
-                                                (8, 0.7, 2, 1)])
+                                                (8, 0.7, 2, 1),
+                                                (8, 0.875, 2, 1), (8, 0.375, 3, 1), (8, 0.25, 3, 0),
+                                                (8, 0.125, 3, 1), (8, 0.0, 4, 1),
+                                                (12, 0.25, 2, 1), (14, 0.5, 2, 1),
+                                                (16, 0.9375, 2, 1), (16, 0.0, 3, 0),
+                                                (2, 0.5, 2, 1), (10, 0.05, 3, 1)])
 def test_patch_search_matches_numpy(oracle, ps, overlap, it, norm):
+    assert oracle.steps(ps, overlap) == ROW_STEP[ps, overlap]
     W, H, C, F = 64, 48, 2, 0
     I0, I1 = shifted_pair(5, H, W)
     Wp, Hp, P0, PX, PY, P1, py0, py1 = oracle.build_pyramids(I0, I1, C, ps)
@@ -303,8 +335,11 @@ def test_var_refine_improves_synthetic_accuracy(oracle):
 # Not in the reference (parity unpinned by construction): the C oracle's
 # restatement is cross-checked by the independent numpy one, plus known answers.
 
-@pytest.mark.parametrize("ps,overlap,it,norm", [(8, 0.625, 4, 1), (4, 0.5, 3, 0), (8, 0.7, 2, 1)])
+@pytest.mark.parametrize("ps,overlap,it,norm", [(8, 0.625, 4, 1), (4, 0.5, 3, 0), (8, 0.7, 2, 1),
+                                                (8, 0.875, 2, 1), (8, 0.375, 3, 1), (8, 0.125, 3, 0),
+                                                (8, 0.0, 4, 1), (12, 0.0, 3, 1)])
 def test_paper_mode_matches_numpy(oracle, ps, overlap, it, norm):
+    assert oracle.steps(ps, overlap) == ROW_STEP[ps, overlap]
     W, H, C, F = 64, 48, 2, 0
     I0, I1 = shifted_pair(15, H, W)
     Wp, Hp, P0, PX, PY, P1, py0, py1 = oracle.build_pyramids(I0, I1, C, ps)

@@ -52,6 +52,22 @@ def test_float64_against_f32(case):
         assert np.array_equal(u32.view(np.uint32), uy.view(np.uint32))
 
 
+def test_tile_layout_table_for_every_grid_step():
+    """The kernel table in tests/test_gpu_fma_levels.py (fma_cases.TILE_TABLE) against the
+    Python restatement of tile_layout, for every grid step patch size 8 can have; every
+    step is the step of some case, and launch_ts holds every stride 2 and 8 lanes per
+    patch can get as a template constant (its run-time-stride default is never taken)."""
+    assert {fc.steps(c) for c in fc.CASES} == set(range(1, 9)) == set(fc.TILE_TABLE)
+    for st, (s1, s2, quad, s4, s8) in fc.TILE_TABLE.items():
+        assert fc.lpp1_fits(st) == (s1 is not None), st
+        if s1 is not None:
+            assert fc.tile_layout(st, 1) == (s1, 0), st
+        assert fc.tile_layout(st, 2) == (s2, quad), st
+        assert fc.tile_layout(st, 4) == (s4, 0), st
+        assert fc.tile_layout(st, 8) == (s8, 0), st
+        assert s2 in fc.LAUNCH_TS_STRIDES and s8 in fc.LAUNCH_TS_STRIDES, st
+
+
 @pytest.mark.parametrize("mutation", s64.MUTATIONS)
 def test_acceptance_rejects_mutation(mutation):
     rejected = {}
