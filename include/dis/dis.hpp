@@ -12,6 +12,9 @@
 //                             colour frames in (set_frame_format: BGR / RGB(A)
 //                             u8 reduced to gray on the GPU) and that
 //                             conversion alone
+//   dis::Yuv420, dis::yuv420ToFrames, dis::framesToYuv420
+//                             4:2:0 video surfaces (NV12, NV21, I420, YV12) to
+//                             frames and back, in exact integer arithmetic
 //   dis::Border, dis::flowWarp
 //                             u8 images warped back by a flow field (f32 or f16)
 //   dis::flowInterp, dis::flowInterpWorkspace
@@ -321,6 +324,77 @@ inline void framesToGray(const uint8_t* src, FrameFormat format, int n, int widt
 {
     check(dis_frames_to_gray_u8(src, src_stride, src_image_stride, static_cast<int>(format), n, width, height, dst,
                                 dst_stride, dst_image_stride, where, stream, device));
+}
+
+// 4:2:0 video surfaces (dis_yuv420_to_frames_u8 / dis_frames_to_yuv420_u8): the
+// matrix and the range of the conversion, and a view of n surfaces of W x H
+// pixels (both even) -- where the Y plane and the Cb and Cr samples lie. The
+// makers describe one buffer per layout: the Y plane with rows `stride` bytes
+// apart (0 = width), then H/2 rows of Cb/Cr pairs (nv12; nv21: Cr/Cb pairs), or
+// the Cb plane and the Cr plane with rows stride/2 apart (i420; yv12: Cr, then
+// Cb); image k of n lies stride * H * 3/2 bytes after image k - 1. y is a gray
+// frame stack as it is: calc(n, view.y, ..., view.y_stride, view.y_image_stride).
+enum class YuvMatrix { BT601 = DIS_YUV_BT601, BT709 = DIS_YUV_BT709 };
+enum class YuvRange { LIMITED = DIS_YUV_LIMITED, FULL = DIS_YUV_FULL };
+struct Yuv420 {
+    uint8_t* y;
+    uint8_t* cb;
+    uint8_t* cr;
+    int width, height;
+    size_t y_stride, y_image_stride, c_stride, c_image_stride;
+    int c_step;  // 1: planar, 2: interleaved
+
+    static Yuv420 nv12(uint8_t* p, int width, int height, size_t stride = 0)
+    {
+        const size_t s = stride ? stride : static_cast<size_t>(width), img = s * height * 3 / 2;
+        uint8_t* const c = p ? p + s * height : nullptr;
+        return {p, c, c ? c + 1 : nullptr, width, height, s, img, s, img, 2};
+    }
+    static Yuv420 nv21(uint8_t* p, int width, int height, size_t stride = 0)
+    {
+        Yuv420 v = nv12(p, width, height, stride);
+        std::swap(v.cb, v.cr);
+        return v;
+    }
+    static Yuv420 i420(uint8_t* p, int width, int height, size_t stride = 0)
+    {
+        const size_t s = stride ? stride : static_cast<size_t>(width), img = s * height * 3 / 2;
+        uint8_t* const c = p ? p + s * height : nullptr;
+        return {p, c, c ? c + (s / 2) * (height / 2) : nullptr, width, height, s, img, s / 2, img, 1};
+    }
+    static Yuv420 yv12(uint8_t* p, int width, int height, size_t stride = 0)
+    {
+        Yuv420 v = i420(p, width, height, stride);
+        std::swap(v.cb, v.cr);
+        return v;
+    }
+};
+
+// n surfaces to n W x H frames of `format` (dst_stride in bytes, 0 = tight), on
+// the GPU, by the exact integer arithmetic of dis_abi.h: nearest chroma, `alpha`
+// in the fourth sample of BGRA8 / RGBA8; a GRAY8 target reads no chroma.
+inline void yuv420ToFrames(const Yuv420& src, int n, uint8_t* dst, FrameFormat format,
+                           YuvMatrix matrix = YuvMatrix::BT601, YuvRange range = YuvRange::LIMITED, int alpha = 255,
+                           size_t dst_stride = 0, size_t dst_image_stride = 0, dis_mem where = DIS_MEM_HOST,
+                           void* stream = nullptr, int device = 0)
+{
+    check(dis_yuv420_to_frames_u8(src.y, src.y_stride, src.y_image_stride, src.cb, src.cr, src.c_stride,
+                                  src.c_image_stride, src.c_step, static_cast<int>(matrix), static_cast<int>(range), n,
+                                  src.width, src.height, dst, dst_stride, dst_image_stride, static_cast<int>(format),
+                                  alpha, where, stream, device));
+}
+
+// n W x H frames of `format` to n surfaces: Y per pixel, Cb and Cr from each
+// 2 x 2 block's sums. With BT601 and FULL the Y plane is framesToGray's image.
+inline void framesToYuv420(const uint8_t* src, FrameFormat format, int n, const Yuv420& dst,
+                           YuvMatrix matrix = YuvMatrix::BT601, YuvRange range = YuvRange::LIMITED,
+                           size_t src_stride = 0, size_t src_image_stride = 0, dis_mem where = DIS_MEM_HOST,
+                           void* stream = nullptr, int device = 0)
+{
+    check(dis_frames_to_yuv420_u8(src, src_stride, src_image_stride, static_cast<int>(format),
+                                  static_cast<int>(matrix), static_cast<int>(range), n, dst.width, dst.height, dst.y,
+                                  dst.y_stride, dst.y_image_stride, dst.cb, dst.cr, dst.c_stride, dst.c_image_stride,
+                                  dst.c_step, where, stream, device));
 }
 
 // Backward warp (dis_flow_warp_u8) of n W x H u8 images of `channels` (1, 3, 4)

@@ -211,6 +211,77 @@ dis_status dis_frames_to_gray_u8(const uint8_t* src, size_t src_stride, size_t s
                                  uint8_t* dst, size_t dst_stride, size_t dst_image_stride,
                                  dis_mem where, void* stream, int device);
 
+/* 4:2:0 video surfaces in and out (no context; added within ABI v8: purely
+ * additive): n surfaces of W x H pixels, W and H even -- a Y plane of W x H
+ * bytes and one Cb and one Cr sample per 2 x 2 block -- to n W x H frames of
+ * `frame_format` (any dis_frame_format; the enum itself does not grow), and
+ * back. What a video decoder delivers and an encoder takes: the Y plane is
+ * already a gray frame with a row stride and an image stride, which
+ * dis_calc_batch_u8 takes as it lies; these two calls are the colour side.
+ *
+ * Layout. Pixel (x, y) of image i has its luma at y_ptr + i*y_image_stride +
+ * y*y_stride + x; the chroma of block (X, Y) is at cb + i*c_image_stride +
+ * Y*c_stride + X*c_step, and at cr likewise. c_step is 1 for planar layouts and
+ * 2 for interleaved ones. NV12 in one buffer: cb = y + y_stride*H, cr = cb + 1,
+ * c_step = 2, c_stride = y_stride, both image strides y_stride*H*3/2; NV21 swaps
+ * cb and cr; I420 and YV12 are the planar forms (c_step = 1, the Cb plane first,
+ * or the Cr plane). Strides in bytes; 0 means W and y_stride*H for the Y plane,
+ * (W/2)*c_step and c_stride*(H/2) for the chroma planes, and W*channels and
+ * stride*H for the frames; otherwise at least that.
+ *
+ * Arithmetic: integers only, signed 32 bits, >> the arithmetic (floor) shift,
+ * clamp to 0..255. One row per (matrix, range):
+ *                 yoff    yy     rv     gu      gv     bu
+ *   601 full         0  16384  22970  -5638  -11700  29032
+ *   601 limited     16  19077  26149  -6419  -13320  33050
+ *   709 full         0  16384  25802  -3069   -7670  30402
+ *   709 limited     16  19077  29372  -3494   -8731  34610
+ *                 Y <- (R,G,B)        Cb <- (R,G,B)         Cr <- (R,G,B)
+ *   601 full      4899  9617 1868    -2765 -5427 8192     8192 -6860 -1332
+ *   601 limited   4207  8260 1604    -2428 -4768 7196     7196 -6026 -1170
+ *   709 full      3483 11718 1183    -1877 -6315 8192     8192 -7441  -751
+ *   709 limited   2991 10064 1016    -1649 -5547 7196     7196 -6536  -660
+ * (the standards' coefficients times 2^14, rounded to nearest, green adjusted so
+ * that a Y row sums to 16384 or 14071 and a chroma row to 0).
+ * To frames: pixel (x, y) takes Y(x, y) and the chroma of block (x>>1, y>>1)
+ * (nearest chroma); c = yy*(Y - yoff) + 8192, u = Cb - 128, v = Cr - 128,
+ *   R = clamp((c + rv*v) >> 14), G = clamp((c + gu*u + gv*v) >> 14), B = clamp((c + bu*u) >> 14);
+ * DIS_FRAME_GRAY8 is clamp(c >> 14): chroma is not read, cb and cr may be NULL.
+ * `alpha` (0..255) fills the fourth sample of BGRA8 / RGBA8 and is ignored
+ * otherwise. From frames: Y = yoff + ((ky.(R,G,B) + 8192) >> 14) per pixel; per
+ * block, with (sR, sG, sB) the sums of its four pixels,
+ *   Cb = clamp((kcb.(sR,sG,sB) + (128 << 16) + (1 << 15)) >> 16), Cr likewise
+ * (one rounding for the average and the conversion); alpha is ignored, and
+ * DIS_FRAME_GRAY8 is R = G = B = v. Gray gives Cb = Cr = 128 exactly; with 601
+ * full, Y is dis_frames_to_gray_u8's byte.
+ *
+ * Refused with DIS_ERR_INVALID_ARGUMENT, before any device call: a null
+ * pointer (except cb / cr with a GRAY8 target); n, width or height < 1, an odd
+ * width or height, a width or height above 2^24; an unknown frame_format,
+ * matrix, range or where; c_step other than 1 or 2; alpha outside 0..255;
+ * strides smaller than a row / an image; any overlap of an output plane with
+ * an input or with another output plane (plane by plane and image by image when
+ * the planes share one image stride, as those of one buffer do; cb and cr one
+ * byte apart with c_step 2 are one plane); more work than one launch's grid
+ * holds. No pointer needs any alignment: each of the three sides (Y, chroma,
+ * frames) moves in 16-byte groups when its bases and strides are multiples of
+ * 16 (planar chroma: in 8-byte groups, multiples of 8), byte by byte otherwise;
+ * same bytes. Only samples are read and written: no padding byte of any plane
+ * is touched. Host pointers: synchronous, staged through HIP device `device`;
+ * device pointers: asynchronous on `stream`, one launch, no allocation. */
+typedef enum dis_yuv_matrix { DIS_YUV_BT601 = 0, DIS_YUV_BT709 = 1 } dis_yuv_matrix;
+typedef enum dis_yuv_range { DIS_YUV_LIMITED = 0, DIS_YUV_FULL = 1 } dis_yuv_range;
+dis_status dis_yuv420_to_frames_u8(const uint8_t* y, size_t y_stride, size_t y_image_stride,
+                                   const uint8_t* cb, const uint8_t* cr, size_t c_stride, size_t c_image_stride,
+                                   int c_step, int matrix, int range, int n, int width, int height,
+                                   uint8_t* dst, size_t dst_stride, size_t dst_image_stride, int frame_format,
+                                   int alpha, dis_mem where, void* stream, int device);
+dis_status dis_frames_to_yuv420_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int frame_format,
+                                   int matrix, int range, int n, int width, int height,
+                                   uint8_t* y, size_t y_stride, size_t y_image_stride,
+                                   uint8_t* cb, uint8_t* cr, size_t c_stride, size_t c_image_stride, int c_step,
+                                   dis_mem where, void* stream, int device);
+
 /* One pair: u8 grayscale frames (row stride `stride` bytes, 0 = width; colour
  * frames under dis_set_frame_format, 0 = width * channels) to a
  * full-resolution W x H x 2 flow, (u,v) interleaved, row-major: floats, or

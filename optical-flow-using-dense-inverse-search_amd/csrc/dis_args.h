@@ -378,4 +378,101 @@ inline const char* check_stabilize_buffers(uintptr_t pair_params, uintptr_t corr
     return check_disjoint(r, 1, 4, why);
 }
 
+// dis_yuv420_to_frames_u8 / dis_frames_to_yuv420_u8: n 4:2:0 surfaces of W x H
+// pixels (both even): a Y plane of W x H bytes and W/2 x H/2 Cb and Cr samples,
+// the sample of block (X, Y) at Y * c_stride + X * c_step (c_step 1: planar,
+// 2: interleaved). Strides in bytes; 0 means W and stride * H for the Y plane,
+// (W/2) * c_step and c_stride * (H/2) for the chroma planes. y_bytes / c_bytes
+// end with ONE image's last sample (of the plane a chroma pointer addresses).
+constexpr int kYuvStripW = 16;  // a lane converts 16 x 2 pixels
+constexpr int kYuvThreads = 256;
+struct Yuv420Layout {
+    size_t y_stride, y_image_stride, c_stride, c_image_stride;
+    size_t y_bytes, c_bytes;
+};
+inline const char* check_yuv420_layout(int n, int width, int height, int c_step, size_t y_stride, size_t y_image_stride,
+                                       size_t c_stride, size_t c_image_stride, Yuv420Layout* out)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide)) return why;
+    if ((width | height) & 1) return "width and height must be even (4:2:0)";
+    if (c_step != 1 && c_step != 2) return "c_step must be 1 (planar) or 2 (interleaved)";
+    ImageStack ys, cs;
+    if (check_image_stack(width, height, 1, n, y_stride, y_image_stride, &ys))
+        return "y_stride or y_image_stride smaller than a row / an image (or too large)";
+    if (check_image_stack(width / 2, height / 2, c_step, n, c_stride, c_image_stride, &cs))
+        return "c_stride or c_image_stride smaller than a row / an image (or too large)";
+    *out = {ys.stride, ys.image_stride, cs.stride, cs.image_stride,
+            (size_t)(height - 1) * ys.stride + (size_t)width,
+            (size_t)(height / 2 - 1) * cs.stride + (size_t)(width / 2 - 1) * c_step + 1};
+    return nullptr;
+}
+
+// Blocks of either launch (a lane per 16 x 2 pixels); -1 when they exceed a grid.
+inline long long yuv420_blocks(int n, int width, int height)
+{
+    if (n < 1 || width < 2 || height < 2) return -1;
+    const long long cw = ((long long)width + kYuvStripW - 1) / kYuvStripW, rows = height / 2;
+    if (n > 0x7fffffffLL * kYuvThreads / cw / rows) return -1;
+    return ((long long)n * rows * cw + kYuvThreads - 1) / kYuvThreads;
+}
+
+// A plane of n images: image i occupies [p + i * image_stride, ... + image_bytes),
+// image_bytes <= image_stride (an absent plane has p = 0 and no bytes).
+struct PlaneStack {
+    uintptr_t p;
+    size_t image_stride, image_bytes;
+    const char* name;
+};
+
+// Two such planes share a byte. With one image stride S (the planes of an NV12
+// or I420 surface lie image by image in one buffer, each in the gaps of the
+// others) it is exact: with a.p <= b.p and d = b.p - a.p, image i of a meets
+// image j = i - k of b iff k * S + a.bytes > d and k * S < d + b.bytes, which only
+// k = d / S and k + 1 can satisfy (bytes <= S). With two image strides the
+// whole extents are compared (planes so laid out are refused even where their
+// images happen to miss each other).
+inline bool plane_stacks_overlap(const PlaneStack& a, const PlaneStack& b, int n)
+{
+    if (!a.p || !b.p || !a.image_bytes || !b.image_bytes || n < 1) return false;
+    if (a.p > b.p) return plane_stacks_overlap(b, a, n);
+    const size_t m = (size_t)(n - 1);
+    if (n == 1 || a.image_stride != b.image_stride)
+        return ranges_overlap(a.p, m * a.image_stride + a.image_bytes, b.p, m * b.image_stride + b.image_bytes);
+    const size_t S = a.image_stride, d = b.p - a.p, k = d / S, rem = d % S;
+    if (k <= m && rem < a.image_bytes) return true;              // k: image k of a reaches into image 0 of b
+    return k + 1 <= m && S - rem < b.image_bytes;                // k + 1: image 0 of b reaches into image k + 1 of a
+}
+
+// The planes of a conversion call: r[0 .. nin) are read, r[nin .. n_planes)
+// written; every written plane must be disjoint from every read one and from
+// every other written one. The caller passes the Cb and Cr of one interleaved
+// plane (c_step 2, one byte apart) as ONE plane: yuv420_chroma_planes. The
+// first offending pair, by name.
+inline const char* check_plane_stacks(const PlaneStack* r, int nin, int n_planes, int n, PairMessage* why)
+{
+    for (int o = nin; o < n_planes; ++o)
+        for (int k = 0; k < n_planes; ++k)
+            if ((k < nin || k > o) && plane_stacks_overlap(r[o], r[k], n)) {
+                const NamedRange pair[2] = {{1, 1, r[k].name}, {1, 1, r[o].name}};
+                return check_disjoint(pair, 1, 2, why);
+            }
+    return nullptr;
+}
+
+// The chroma planes of a surface as 1 or 2 entries of such a list (returns how
+// many): Cb and Cr one byte apart with c_step 2 are the two halves of one
+// interleaved plane, which begins at the lower of the two and is one byte
+// longer; otherwise each is a plane of its own (with c_step 2 it then spans
+// the bytes between its samples too). Null pointers give absent planes.
+inline int yuv420_chroma_planes(uintptr_t cb, uintptr_t cr, int c_step, const Yuv420Layout& l, PlaneStack* out)
+{
+    if (cb && cr && c_step == 2 && (cb + 1 == cr || cr + 1 == cb)) {
+        out[0] = {cb < cr ? cb : cr, l.c_image_stride, l.c_bytes + 1, "cb/cr"};
+        return 1;
+    }
+    out[0] = {cb, l.c_image_stride, cb ? l.c_bytes : 0, "cb"};
+    out[1] = {cr, l.c_image_stride, cr ? l.c_bytes : 0, "cr"};
+    return 2;
+}
+
 }  // namespace dis

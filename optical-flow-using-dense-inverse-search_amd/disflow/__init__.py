@@ -65,6 +65,11 @@ _FRAME_FORMATS = {"gray": FRAME_GRAY8, "bgr": FRAME_BGR8, "rgb": FRAME_RGB8, "bg
                   "rgba": FRAME_RGBA8}
 _FRAME_CHANNELS = {FRAME_GRAY8: 1, FRAME_BGR8: 3, FRAME_RGB8: 3, FRAME_BGRA8: 4, FRAME_RGBA8: 4}
 
+YUV_BT601, YUV_BT709 = 0, 1  # dis_yuv_matrix
+YUV_LIMITED, YUV_FULL = 0, 1  # dis_yuv_range
+_YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709, YUV_BT601: YUV_BT601, YUV_BT709: YUV_BT709}
+_YUV_RANGES = {"limited": YUV_LIMITED, "full": YUV_FULL, YUV_LIMITED: YUV_LIMITED, YUV_FULL: YUV_FULL}
+
 
 def _frame_format(fmt) -> int:
     """dis_frame_format of "gray" / "bgr" / "rgb" / "bgra" / "rgba" (or of the enum's
@@ -116,6 +121,7 @@ EXPORTED_SYMBOLS = (
     "dis_flow_fit_motion_workspace", "dis_flow_fit_motion", "dis_motion_to_flow",
     "dis_denoise_weights", "dis_temporal_denoise_u8",
     "dis_motion_stabilize", "dis_warp_motion_u8",
+    "dis_yuv420_to_frames_u8", "dis_frames_to_yuv420_u8",
 )
 
 
@@ -259,6 +265,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_warp_motion_u8"):  # (added within v8)
             L.dis_motion_stabilize.argtypes = [V, I, I, I, I, ctypes.c_float, ctypes.c_float, V, V, P(I)]
             L.dis_warp_motion_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, V, V, I, V, I]
+        if hasattr(L, "dis_yuv420_to_frames_u8"):  # (added within v8)
+            L.dis_yuv420_to_frames_u8.argtypes = [V, Z, Z, V, V, Z, Z, I, I, I, I, I, I, V, Z, Z, I, I, I, V, I]
+            L.dis_frames_to_yuv420_u8.argtypes = [V, Z, Z, I, I, I, I, I, I, V, Z, Z, V, V, Z, Z, I, I, V, I]
         L.dis_stage_size.argtypes = [V, I, I, P(Z)]
         L.dis_debug_dump.argtypes = [V, I, I, I, V, Z]
         L.dis_set_kernel_timing.argtypes = [V, I]
@@ -993,6 +1002,160 @@ def frames_to_gray_device(src_ptr: int, frame_format, n: int, width: int, height
     fmt = _frame_format(frame_format)
     _check(lib().dis_frames_to_gray_u8(src_ptr, src_stride, src_image_stride, fmt, n, width, height, dst_ptr,
                                        dst_stride, dst_image_stride, MEM_DEVICE, stream or None, device))
+
+
+def _yuv_args(frame_format, matrix, range, alpha=255):
+    """(dis_frame_format, dis_yuv_matrix, dis_yuv_range, alpha) of the names (or
+    the enums' own values); ValueError for anything else."""
+    fmt = _frame_format(frame_format)
+    if isinstance(matrix, bool) or matrix not in _YUV_MATRICES:
+        raise ValueError(f"matrix must be 'bt601' or 'bt709', not {matrix!r}")
+    if isinstance(range, bool) or range not in _YUV_RANGES:
+        raise ValueError(f"range must be 'limited' or 'full', not {range!r}")
+    if not isinstance(alpha, (int, np.integer)) or isinstance(alpha, bool) or not 0 <= alpha <= 255:
+        raise ValueError(f"alpha must be an integer in [0, 255], not {alpha!r}")
+    return fmt, _YUV_MATRICES[matrix], _YUV_RANGES[range], int(alpha)
+
+
+def _surface(buf):
+    """A host 4:2:0 surface buffer, u8 (n, H*3//2, W) or (H*3//2, W) (NV12: the Y
+    plane, then H/2 rows of Cb/Cr pairs; I420: the Y plane, the Cb plane, the Cr
+    plane) -> (contiguous (n, H*3//2, W) array, single, n, W, H)."""
+    a = np.asarray(buf)
+    if a.dtype != np.uint8:
+        raise ValueError(f"surface dtype must be uint8, not {a.dtype}")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"a 4:2:0 surface buffer must be (H*3//2, W) or (n, H*3//2, W), not {a.shape}")
+    rows, W = a.shape[-2:]
+    H = rows * 2 // 3
+    if rows < 3 or rows % 3 or H % 2 or W < 2 or W % 2:
+        raise ValueError(f"a 4:2:0 surface buffer has H*3//2 rows of W bytes with even W and H, not {a.shape}")
+    single = a.ndim == 2
+    a = np.ascontiguousarray(a[None] if single else a)
+    if a.shape[0] < 1:
+        raise ValueError("no surface")
+    return a, single, a.shape[0], W, H
+
+
+def _packed(frames, fmt):
+    """Host frames of dis_frame_format fmt with even sides -> (contiguous
+    (n, H, W[, C]) array, single, n, W, H)."""
+    a = np.asarray(frames)
+    if a.dtype != np.uint8:
+        raise ValueError(f"frames dtype must be uint8, not {a.dtype}")
+    C = _FRAME_CHANNELS[fmt]
+    lead = a.ndim - (1 if C > 1 else 0)
+    if lead not in (2, 3) or (C > 1 and a.shape[-1] != C):
+        what = "(H, W) or (n, H, W)" if C == 1 else f"(H, W, {C}) or (n, H, W, {C})"
+        raise ValueError(f"frames of this format must be {what}, not {a.shape}")
+    single = lead == 2
+    a = np.ascontiguousarray(a[None] if single else a)
+    n, H, W = a.shape[:3]
+    if n < 1 or H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 needs even sides, not {W} x {H}")
+    return a, single, n, W, H
+
+
+def _surface_planes(base, W, H, interleaved, swap):
+    """(cb, cr, c_step, c_stride) of a tight one-buffer surface at `base`: NV12 /
+    NV21 (interleaved) or I420 / YV12; swap: the Cr sample (plane) comes first."""
+    c0 = base + W * H
+    c1 = c0 + (1 if interleaved else (W // 2) * (H // 2))
+    cb, cr = (c1, c0) if swap else (c0, c1)
+    return cb, cr, (2 if interleaved else 1), (W if interleaved else W // 2)
+
+
+def _surface_to_frames(buf, frame_format, matrix, range, alpha, device, interleaved):
+    fmt, mat, rng, alpha = _yuv_args(frame_format, matrix, range, alpha)
+    a, single, n, W, H = _surface(buf)
+    C = _FRAME_CHANNELS[fmt]
+    out = np.empty((n, H, W) + ((C,) if C > 1 else ()), np.uint8)
+    cb, cr, step, cst = _surface_planes(_ptr(a), W, H, interleaved, False)
+    img = W * H * 3 // 2
+    _check(lib().dis_yuv420_to_frames_u8(_ptr(a), W, img, cb, cr, cst, img, step, mat, rng, n, W, H, _ptr(out), 0, 0,
+                                         fmt, alpha, MEM_HOST, None, device))
+    return out[0] if single else out
+
+
+def _frames_to_surface(frames, frame_format, matrix, range, device, interleaved):
+    fmt, mat, rng, _ = _yuv_args(frame_format, matrix, range)
+    a, single, n, W, H = _packed(frames, fmt)
+    out = np.empty((n, H * 3 // 2, W), np.uint8)
+    cb, cr, step, cst = _surface_planes(_ptr(out), W, H, interleaved, False)
+    img = W * H * 3 // 2
+    _check(lib().dis_frames_to_yuv420_u8(_ptr(a), 0, 0, fmt, mat, rng, n, W, H, _ptr(out), W, img, cb, cr, cst, img,
+                                         step, MEM_HOST, None, device))
+    return out[0] if single else out
+
+
+def nv12_to_frames(buf: np.ndarray, frame_format, matrix="bt601", range="limited", alpha: int = 255,
+                   device: int = 0) -> np.ndarray:
+    """dis_yuv420_to_frames_u8 on host NV12 surfaces: u8 (H*3//2, W) or
+    (n, H*3//2, W), the Y plane followed by H/2 rows of Cb/Cr pairs -> frames of
+    `frame_format` ((..., H, W, C), "gray": (..., H, W)) on the GPU, by the exact
+    integer arithmetic of include/dis_abi.h (nearest chroma). matrix "bt601" /
+    "bt709", range "limited" / "full"; alpha fills the fourth sample."""
+    return _surface_to_frames(buf, frame_format, matrix, range, alpha, device, True)
+
+
+def i420_to_frames(buf: np.ndarray, frame_format, matrix="bt601", range="limited", alpha: int = 255,
+                   device: int = 0) -> np.ndarray:
+    """As nv12_to_frames for I420 surfaces: the Y plane, then the W/2 x H/2 Cb
+    plane, then the Cr plane, each tight, in H*3//2 rows of W bytes."""
+    return _surface_to_frames(buf, frame_format, matrix, range, alpha, device, False)
+
+
+def frames_to_nv12(frames: np.ndarray, frame_format, matrix="bt601", range="limited", device: int = 0) -> np.ndarray:
+    """dis_frames_to_yuv420_u8 on host frames with even sides ((H, W, C) or
+    (n, H, W, C); "gray": (H, W) or (n, H, W)) -> NV12 surfaces, u8 (H*3//2, W) /
+    (n, H*3//2, W). Y per pixel, Cb and Cr from each 2 x 2 block's sums. With
+    "bt601" and "full" the Y plane is frames_to_gray's image."""
+    return _frames_to_surface(frames, frame_format, matrix, range, device, True)
+
+
+def frames_to_i420(frames: np.ndarray, frame_format, matrix="bt601", range="limited", device: int = 0) -> np.ndarray:
+    """As frames_to_nv12, to I420 surfaces (the Y, Cb and Cr planes in turn)."""
+    return _frames_to_surface(frames, frame_format, matrix, range, device, False)
+
+
+def nv12_luma(buf):
+    """The Y planes of NV12 (or I420) surface buffers (H*3//2, W) / (n, H*3//2, W):
+    a strided view (H, W) / (n, H, W), no copy -- numpy arrays and torch tensors
+    alike. They are gray frames with row stride W and image stride W*H*3//2,
+    which calc_device(..., stride, pair_stride) takes in place."""
+    if len(buf.shape) not in (2, 3):
+        raise ValueError(f"a 4:2:0 surface buffer must be (H*3//2, W) or (n, H*3//2, W), not {tuple(buf.shape)}")
+    rows, W = buf.shape[-2:]
+    H = rows * 2 // 3
+    if rows < 3 or rows % 3 or H % 2 or W < 2 or W % 2:
+        raise ValueError(f"a 4:2:0 surface buffer has H*3//2 rows of W bytes with even W and H, not {tuple(buf.shape)}")
+    return buf[..., :H, :]
+
+
+def yuv420_to_frames_device(y_ptr: int, cb_ptr: int, cr_ptr: int, c_step: int, n: int, width: int, height: int,
+                            dst_ptr: int, frame_format, matrix="bt601", range="limited", alpha: int = 255,
+                            y_stride: int = 0, y_image_stride: int = 0, c_stride: int = 0, c_image_stride: int = 0,
+                            dst_stride: int = 0, dst_image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_yuv420_to_frames_u8 on raw device pointers (strides in bytes, 0 = tight),
+    asynchronous on `stream`. NV12: cb_ptr = y_ptr + y_stride * height,
+    cr_ptr = cb_ptr + 1, c_step = 2, c_stride = y_stride; I420: c_step = 1. With a
+    "gray" target cb_ptr and cr_ptr may be 0."""
+    fmt, mat, rng, alpha = _yuv_args(frame_format, matrix, range, alpha)
+    _check(lib().dis_yuv420_to_frames_u8(y_ptr, y_stride, y_image_stride, cb_ptr or None, cr_ptr or None, c_stride,
+                                         c_image_stride, c_step, mat, rng, n, width, height, dst_ptr, dst_stride,
+                                         dst_image_stride, fmt, alpha, MEM_DEVICE, stream or None, device))
+
+
+def frames_to_yuv420_device(src_ptr: int, frame_format, n: int, width: int, height: int, y_ptr: int, cb_ptr: int,
+                            cr_ptr: int, c_step: int, matrix="bt601", range="limited", src_stride: int = 0,
+                            src_image_stride: int = 0, y_stride: int = 0, y_image_stride: int = 0, c_stride: int = 0,
+                            c_image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_frames_to_yuv420_u8 on raw device pointers (strides in bytes, 0 = tight),
+    asynchronous on `stream`."""
+    fmt, mat, rng, _ = _yuv_args(frame_format, matrix, range)
+    _check(lib().dis_frames_to_yuv420_u8(src_ptr, src_stride, src_image_stride, fmt, mat, rng, n, width, height,
+                                         y_ptr, y_stride, y_image_stride, cb_ptr or None, cr_ptr or None, c_stride,
+                                         c_image_stride, c_step, MEM_DEVICE, stream or None, device))
 
 
 def read_flo(path: str, channels: int = 2) -> np.ndarray:
