@@ -584,6 +584,66 @@ inline void warpMotion(const uint8_t* src, int channels, const float* params, in
                              static_cast<int>(border), dst, valid, where, stream, device));
 }
 
+// The homography (eight-parameter) family beside the affine one above, for a
+// camera that rotates: with g = p6 x + p7 y, u = (p0 + p1 x + p2 y - x g) / (1 + g)
+// and v = (p3 + p4 x + p5 y - y g) / (1 + g) over pixel indices.
+// fitHomography is fitMotion without a model (dis_flow_fit_homography; params:
+// n * 8 floats, NaN when a fit fails; device pointers need
+// fitHomographyWorkspace bytes); homographyToFlow is motionToFlow
+// (dis_homography_to_flow; a pixel behind the model's horizon is NaN);
+// stabilizePathHomography is stabilizePath (dis_homography_stabilize;
+// (n_frames - 1) * 8 floats in, n_frames * 8 out); warpHomography is warpMotion
+// (dis_warp_homography_u8; bit for bit homographyToFlow followed by flowWarp).
+inline size_t fitHomographyWorkspace(int n, int width, int height)
+{
+    size_t bytes = 0;
+    check(dis_flow_fit_homography_workspace(n, width, height, &bytes));
+    return bytes;
+}
+inline void fitHomography(const float* flow, int n, int width, int height, float* params, int iterations = 3,
+                          float threshold = 1.0f, const uint8_t* mask = nullptr, uint32_t* info = nullptr,
+                          uint8_t* inliers = nullptr, void* workspace = nullptr, dis_mem where = DIS_MEM_HOST,
+                          void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fit_homography(flow, DIS_FLOW_F32, mask, n, width, height, iterations, threshold, params, info, inliers,
+                                  workspace, where, stream, device));
+}
+inline void fitHomography(const half_bits* flow, int n, int width, int height, float* params, int iterations = 3,
+                          float threshold = 1.0f, const uint8_t* mask = nullptr, uint32_t* info = nullptr,
+                          uint8_t* inliers = nullptr, void* workspace = nullptr, dis_mem where = DIS_MEM_HOST,
+                          void* stream = nullptr, int device = 0)
+{
+    check(dis_flow_fit_homography(flow, DIS_FLOW_F16, mask, n, width, height, iterations, threshold, params, info, inliers,
+                                  workspace, where, stream, device));
+}
+inline void homographyToFlow(const float* params, int n, int width, int height, float* out, dis_mem where = DIS_MEM_HOST,
+                             void* stream = nullptr, int device = 0)
+{
+    check(dis_homography_to_flow(params, n, width, height, out, DIS_FLOW_F32, where, stream, device));
+}
+inline void homographyToFlow(const float* params, int n, int width, int height, half_bits* out,
+                             dis_mem where = DIS_MEM_HOST, void* stream = nullptr, int device = 0)
+{
+    check(dis_homography_to_flow(params, n, width, height, out, DIS_FLOW_F16, where, stream, device));
+}
+inline std::vector<float> stabilizePathHomography(const float* pair_params, int n_frames, int width, int height,
+                                                  int radius, float sigma, float zoom = 1.0f, uint8_t* status = nullptr,
+                                                  int* replaced = nullptr)
+{
+    std::vector<float> corrections(n_frames > 0 ? (size_t)n_frames * 8 : 8);
+    check(dis_homography_stabilize(pair_params, n_frames, width, height, radius, sigma, zoom, corrections.data(), status,
+                                   replaced));
+    return corrections;
+}
+inline void warpHomography(const uint8_t* src, int channels, const float* params, int n, int width, int height,
+                           uint8_t* dst, Border border = Border::REPLICATE, uint8_t* valid = nullptr,
+                           size_t src_stride = 0, size_t src_image_stride = 0, dis_mem where = DIS_MEM_HOST,
+                           void* stream = nullptr, int device = 0)
+{
+    check(dis_warp_homography_u8(src, src_stride, src_image_stride, channels, params, n, width, height,
+                                 static_cast<int>(border), dst, valid, where, stream, device));
+}
+
 // Motion-compensated temporal denoising (dis_temporal_denoise_u8) of n W x H u8
 // images of `channels` (1, 3, 4) interleaved samples, on the GPU: each of the
 // k_neighbours (1..8) frames is warped to cur by its flow (cur -> neighbour k)

@@ -914,6 +914,125 @@ dis_status dis_warp_motion_u8(const uint8_t* src, size_t src_stride, size_t src_
                               uint8_t* dst, uint8_t* valid /* may be NULL */,
                               dis_mem where, void* stream, int device);
 
+/* The homography (eight-parameter) motion family (added within ABI v8, additive;
+ * no context): dis_flow_fit_motion, dis_motion_to_flow, dis_warp_motion_u8 and
+ * dis_motion_stabilize again for projective models -- a camera that rotates.
+ * Eight floats per model; p0..p5 have the affine family's meaning, p6 and p7 are
+ * the projective row. In frame coordinates (x, y the pixel indices), with
+ * g = p6*x + p7*y and d = 1 + g:
+ *   u = (((p0 + p1*x) + p2*y) - x*g) / d,   v = (((p3 + p4*x) + p5*y) - y*g) / d,
+ * the deviation form of the matrix [[1+p1 p2 p0] [p4 1+p5 p3] [p6 p7 1]].
+ *
+ * dis_flow_fit_homography: dis_flow_fit_motion without `model`; params is n*8
+ * floats; flow, mask, iterations, threshold, info (n*4 words), inliers, the
+ * workspace rule, the refusals and the launch counts are those of
+ * dis_flow_fit_motion (2 * (iterations + 1) launches and one more for inliers).
+ * dis_flow_fit_homography_workspace returns n * (chunks*27 + 16) * 8 bytes.
+ * The result is defined by its arithmetic, all of it f64 with every operation
+ * rounded on its own.
+ * Coordinates: cx = (W-1)/2, cy = (H-1)/2; s = the smallest power of two >=
+ * max(W, H, 2)/2; a = (x - cx)/s, b = (y - cy)/s, U = u/s, V = v/s with (u, v)
+ * the pixel's vector widened to double (all exact); A = a + U, B = b + V.
+ * Model: centred, scaled coefficients c0..c7 of the linear system
+ *   U = c0 + c1*a + c2*b - c6*a*A - c7*b*A,  V = c3 + c4*a + c5*b - c6*a*B - c7*b*B.
+ * Terms of a member, in this order (every other pixel: +0.0 27 times), with
+ * aa = a*a, ab = a*b, bb = b*b, aA = a*A, bA = b*A, aB = a*B, bB = b*B,
+ * Q = A*A + B*B:
+ *    0..5   1, a, b, aa, ab, bb
+ *    6..10  aA, bA, aa*A, ab*A, bb*A
+ *   11..15  aB, bB, aa*B, ab*B, bb*B
+ *   16..18  aa*Q, ab*Q, bb*Q
+ *   19..24  U, a*U, b*U, V, a*V, b*V
+ *   25, 26  aA*U + aB*V,  bA*U + bB*V
+ * summed per term in dis_flow_fit_motion's order (256 slots x 64 pixels per
+ * chunk of 16384, eight rounds of adjacent pairs, the chunks in turn).
+ * Solve N c = r by dis_flow_fit_motion's LDL^T and pivot rule (d_j > 2^-20 *
+ * N_jj), N symmetric 8 x 8 with G = [[S0 S1 S2] [S1 S3 S4] [S2 S4 S5]] at rows and
+ * columns 0..2 and again at 3..5, zeros between the two; column 6 rows 0..5 =
+ * (-S6 -S8 -S9 -S11 -S13 -S14), column 7 rows 0..5 = (-S7 -S9 -S10 -S12 -S14
+ * -S15); N66 = S16, N67 = S17, N77 = S18; r = (S19 S20 S21 S22 S23 S24 -S25 -S26).
+ * Members of pass 0: the trusted pixels (dis_flow_fit_motion's test); of pass
+ * j >= 1, and the inliers: the trusted pixels with d > 0 and rU*rU + rV*rV <=
+ * T2/(s*s) against the model c of pass j-1, where g = c6*a + c7*b, d = 1.0 + g,
+ * eU = (((c0 + c1*a) + c2*b) - a*g) / d, eV = (((c3 + c4*a) + c5*b) - b*g) / d,
+ * rU = U - eU, rV = V - eV, T2 = (double)threshold * (double)threshold: the
+ * geometric residual in pixels against the threshold, both scaled by the power
+ * of two s (exact); the bound is inclusive; a NaN model has no members.
+ * The fit fails when a pivot fails, when a coefficient is not finite, or when
+ * d = 1.0 + (c6*a + c7*b) is not > 1/8 at one of the frame's four corners (x in
+ * {0, W-1}, y in {0, H-1}; a design rule: a model whose horizon approaches the
+ * frame is no camera shake, and every later stage divides by d). Then all eight
+ * c are NaN and the later passes have no members and fail likewise.
+ * Output, conjugated back to frame coordinates and normalised by the bottom-
+ * right entry w (d at pixel (0, 0), which the corner rule keeps above 1/8):
+ * ax = cx/s, ay = cy/s, g00 = c6*((0 - cx)/s) + c7*((0 - cy)/s), w = 1.0 + g00,
+ *   p0 = ((((s*c0) - c1*cx) - c2*cy) + cx*g00) / w,  p1 = ((c1 + ax*c6) - g00) / w,
+ *   p2 = (c2 + ax*c7) / w,
+ *   p3 = ((((s*c3) - c4*cx) - c5*cy) + cy*g00) / w,  p4 = (c4 + ay*c6) / w,
+ *   p5 = ((c5 + ay*c7) - g00) / w,  p6 = (c6/s) / w,  p7 = (c7/s) / w,
+ * each rounded once to f32; a failed fit writes the bits 0x7fc00000 eight times.
+ * info and inliers as for dis_flow_fit_motion. */
+dis_status dis_flow_fit_homography_workspace(int n, int width, int height, size_t* bytes);
+dis_status dis_flow_fit_homography(const void* flow, int flow_format, const uint8_t* mask /* may be NULL */,
+                                   int n, int width, int height, int iterations, float threshold,
+                                   float* params /* n*8 */, uint32_t* info /* n*4, may be NULL */,
+                                   uint8_t* inliers /* n*W*H, may be NULL */,
+                                   void* workspace, dis_mem where, void* stream, int device);
+
+/* The field of a homography (added within ABI v8, additive; no context):
+ * dis_motion_to_flow for n*8 parameters, in f32 with every operation rounded on
+ * its own: g = p6*(float)x + p7*(float)y, d = 1.0f + g,
+ *   u = (((p0 + p1*(float)x) + p2*(float)y) - (float)x*g) / d,
+ *   v = (((p3 + p4*(float)x) + p5*(float)y) - (float)y*g) / d,
+ * the divisions correctly rounded. A field with a parameter that is not finite
+ * is the canonical NaN everywhere, and so is a pixel whose d is not > 0 (behind
+ * the horizon). With p6 = p7 = +0.0f the output is bit for bit
+ * dis_motion_to_flow's of p0..p5. Refusals as for dis_motion_to_flow. One launch. */
+dis_status dis_homography_to_flow(const float* params /* n*8 */, int n, int width, int height,
+                                  void* out, int out_format, dis_mem where, void* stream, int device);
+
+/* Backward warp of u8 images by homographies (added within ABI v8, additive; no
+ * context): dis_warp_motion_u8 for n*8 parameters. dst and valid hold, bit for
+ * bit, what dis_homography_to_flow(DIS_FLOW_F32) followed by dis_flow_warp_u8
+ * writes (a pixel with d not > 0 gets every channel 0 and valid 0); no field
+ * exists anywhere. Arguments, strides, borders, valid, refusals and the launch
+ * (one, a block per 64 x 16 pixels) as for dis_warp_motion_u8. */
+dis_status dis_warp_homography_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                                  const float* params /* n*8 */, int n, int width, int height, int border,
+                                  uint8_t* dst, uint8_t* valid /* may be NULL */,
+                                  dis_mem where, void* stream, int device);
+
+/* The camera path of homographies smoothed (added within ABI v8, additive; host
+ * only): dis_motion_stabilize with full 3 x 3 matrices; pair_params is
+ * (n_frames-1)*8 floats, corrections n_frames*8. All of it f64 with every
+ * operation rounded on its own, in this order. A product a.b has the entries
+ * (a_i0*b_0j + a_i1*b_1j) + a_i2*b_2j; norm(m) divides each of the nine entries
+ * by m22.
+ * Pair matrices: A_k = [[1+p1 p2 p0] [p4 1+p5 p3] [p6 p7 1]], each p widened
+ * from f32; a model with any non-finite parameter is replaced by the identity,
+ * and *replaced counts those models.
+ * Path: C_0 = I, C_{k+1} = norm(A_k . C_k).
+ * Weights and smoothed path S_k: dis_motion_stabilize's, per entry, for all nine.
+ * Inverse, by adjugate and determinant: k00 = s11*s22 - s12*s21, k01 = s10*s22 -
+ * s12*s20, k02 = s10*s21 - s11*s20, det = (s00*k00 - s01*k01) + s02*k02; if det
+ * is not finite or |det| <= 2^-20, frame k's correction is eight times +0.0f
+ * and status[k] = 0. Otherwise the rows of the inverse are
+ *   (k00, s02*s21 - s01*s22, s01*s12 - s02*s11) / det,
+ *   (s12*s20 - s10*s22, s00*s22 - s02*s20, s02*s10 - s00*s12) / det,
+ *   (k02, s01*s20 - s00*s21, s00*s11 - s01*s10) / det, each entry divided on its own.
+ * Correction: M_k = norm((C_k . S_k^-1) . Z), Z = [[z 0 cx*(1-z)] [0 z cy*(1-z)]
+ * [0 0 1]] as for dis_motion_stabilize; q = (m02, m00-1, m01, m12, m10, m11-1,
+ * m20, m21), each value rounded once to f32, a q6 or q7 that compares equal to
+ * zero written as +0.0f; status[k] = 1; if any q is not finite the frame falls
+ * back to eight times +0.0f and status 0.
+ * So identity pair models with zoom 1 give all-zero corrections bit for bit,
+ * and affine inputs (p6 = p7 = 0) give q6 = q7 = +0.0f. Refusals as for
+ * dis_motion_stabilize; the path needs 72 bytes of host memory a frame. */
+dis_status dis_homography_stabilize(const float* pair_params /* (n_frames-1)*8 */, int n_frames,
+                                    int width, int height, int radius, float sigma, float zoom,
+                                    float* corrections /* n_frames*8 */, uint8_t* status /* n_frames, may be NULL */,
+                                    int* replaced /* may be NULL */);
+
 /* Motion-compensated temporal denoising of u8 images (added within ABI v8,
  * additive; no context, like dis_flow_warp_u8; no reference counterpart): each
  * of K neighbouring frames is warped to the current one by its flow and blended

@@ -65,7 +65,14 @@
 // default, up to 16), and every frame start .. end is warped by its correction
 // with dis::warpMotion, up to N frames a call. Written as
 // OF_<folder>/frame_NNNN_stab.png, 8-bit grey, colour with --color; the
-// corrections, one "%.9g" line per frame, as OF_<folder>/stab_corrections.txt).
+// corrections, one "%.9g" line per frame, as OF_<folder>/stab_corrections.txt),
+// --homography (the pair's global motion as a homography by dis::fitHomography
+// with its defaults, written as OF_<folder>/frame_NNNN_homography.txt: one line
+// of the eight parameters p0 .. p7, "%.9g" each, nan where the fit failed; with
+// --bidir only the consistent vectors are fitted; and --stabilize R then runs
+// the homography chain: these pair models through dis::stabilizePathHomography
+// and dis::warpHomography, eight values a line in stab_corrections.txt;
+// --motion's names and files are as without it).
 //
 // For img_i in [start, end): reads <folder>/frame_<img_i>.png and frame_<img_i+1>
 // (grayscale, src/main.cpp:118-130), computes the full-resolution flow
@@ -104,7 +111,7 @@ void usage()
                  "patch_overlap patch_norm draw_grid\n"
                  "options: --flo  --batch N  --device D  --paper  --refine K  --bidir  --fb-alpha A1 A2  --warm-start  --warp  "
                  "--interp K  --color  --accumulate  --fill  --motion MODEL  --denoise R SIGMA  "
-                 "--stabilize R  --stab-zoom Z"
+                 "--stabilize R  --stab-zoom Z  --homography"
               << std::endl;
 }
 
@@ -130,6 +137,7 @@ int main(int argc, char** argv)
     float fb_alpha1 = 0.01f, fb_alpha2 = 0.5f;
     int interp = 0;
     bool color = false, accumulate = false, fill = false;
+    bool homography = false;  // --homography: the eight-parameter fit, and --stabilize's chain by it
     std::string motion;  // --motion: the model's name (empty: no fit)
     int denoise = 0;     // --denoise: the radius R (0: off)
     float denoise_sigma = 0.0f;
@@ -160,6 +168,8 @@ int main(int argc, char** argv)
             accumulate = true;
         } else if (a == "--fill") {
             fill = true;
+        } else if (a == "--homography") {
+            homography = true;
         } else if (a == "--motion" && i + 1 < argc) {
             motion = argv[++i];
         } else if (a == "--denoise" && i + 2 < argc) {
@@ -322,13 +332,21 @@ int main(int argc, char** argv)
                 dis::flowFill(flow.data(), n, W, H, filled.data(), mask.data(), fill_level.data(), nullptr, DIS_MEM_HOST,
                               nullptr, device);
             }
-            std::vector<float> motion_params;
-            if (!motion.empty() || stabilize_given) {
+            std::vector<float> motion_params, homography_params;
+            if (!motion.empty() || (stabilize_given && !homography)) {
                 motion_params.resize((size_t)n * 6);
                 dis::fitMotion(flow.data(), n, W, H, motion_params.data(), motion_model, 3, 1.0f,
                                bidir ? mask.data() : nullptr, nullptr, nullptr, nullptr, DIS_MEM_HOST, nullptr, device);
             }
-            if (stabilize_given) pair_models.insert(pair_models.end(), motion_params.begin(), motion_params.end());
+            if (homography) {
+                homography_params.resize((size_t)n * 8);
+                dis::fitHomography(flow.data(), n, W, H, homography_params.data(), 3, 1.0f, bidir ? mask.data() : nullptr,
+                                   nullptr, nullptr, nullptr, DIS_MEM_HOST, nullptr, device);
+            }
+            if (stabilize_given) {
+                const std::vector<float>& m = homography ? homography_params : motion_params;
+                pair_models.insert(pair_models.end(), m.begin(), m.end());
+            }
             std::vector<uint8_t> bgr((size_t)n * W * H * 3);
             dis::check(dis_flow_color(flow.data(), n, W, H, -1.0f, bgr.data(), DIS_MEM_HOST, nullptr, device));
             std::vector<uint8_t> warped, inside;
@@ -400,6 +418,15 @@ int main(int argc, char** argv)
                     if (!f || std::fputs(line, f) < 0 || std::fclose(f) != 0)
                         throw std::runtime_error("cannot write " + base + "_motion.txt");
                 }
+                if (homography) {
+                    const float* m = homography_params.data() + (size_t)k * 8;
+                    char line[192];
+                    std::snprintf(line, sizeof line, "%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", m[0], m[1], m[2], m[3], m[4],
+                                  m[5], m[6], m[7]);
+                    std::FILE* f = std::fopen((base + "_homography.txt").c_str(), "w");
+                    if (!f || std::fputs(line, f) < 0 || std::fclose(f) != 0)
+                        throw std::runtime_error("cannot write " + base + "_homography.txt");
+                }
                 if (fill) {
                     dis::check(dis_write_flo((base + "_filled.flo").c_str(), filled.data() + (size_t)k * W * H * 2, W, H, 2));
                     png::write_gray(base + "_fill.png", fill_level.data() + (size_t)k * W * H, W, H);
@@ -468,15 +495,20 @@ int main(int argc, char** argv)
         if (stabilize_given && eng) {  // --stabilize: every frame of the range onto the smoothed camera path
             const int C = color ? 3 : 1, T = end - start + 1;
             const size_t fsz = (size_t)W * H * C;
-            if (pair_models.size() != (size_t)(T - 1) * 6)
+            const int PM = homography ? 8 : 6;  // parameters of a model
+            if (pair_models.size() != (size_t)(T - 1) * PM)
                 throw std::runtime_error("--stabilize: the frame size changed within the range");
+            const float stab_sigma = (float)std::max(stabilize, 1) / 2.0f;
             const std::vector<float> corr =
-                dis::stabilizePath(pair_models.data(), T, W, H, stabilize, (float)std::max(stabilize, 1) / 2.0f, stab_zoom);
+                homography ? dis::stabilizePathHomography(pair_models.data(), T, W, H, stabilize, stab_sigma, stab_zoom)
+                           : dis::stabilizePath(pair_models.data(), T, W, H, stabilize, stab_sigma, stab_zoom);
             std::FILE* cf = std::fopen((out_dir + "/stab_corrections.txt").c_str(), "w");
             if (!cf) throw std::runtime_error("cannot write " + out_dir + "/stab_corrections.txt");
             for (int t = 0; t < T; ++t) {
-                const float* m = corr.data() + (size_t)t * 6;
-                std::fprintf(cf, "%.9g %.9g %.9g %.9g %.9g %.9g\n", m[0], m[1], m[2], m[3], m[4], m[5]);
+                const float* m = corr.data() + (size_t)t * PM;
+                std::fprintf(cf, "%.9g %.9g %.9g %.9g %.9g %.9g", m[0], m[1], m[2], m[3], m[4], m[5]);
+                if (homography) std::fprintf(cf, " %.9g %.9g", m[6], m[7]);
+                std::fprintf(cf, "\n");
             }
             if (std::fclose(cf) != 0) throw std::runtime_error("cannot write " + out_dir + "/stab_corrections.txt");
             for (int t0 = 0; t0 < T; t0 += batch) {
@@ -496,8 +528,12 @@ int main(int argc, char** argv)
                     if (w != W || h != H) throw std::runtime_error("--stabilize: frame sizes differ within the range");
                     std::copy(px.begin(), px.end(), src.begin() + (size_t)k * fsz);
                 }
-                dis::warpMotion(src.data(), C, corr.data() + (size_t)t0 * 6, n, W, H, dst.data(), dis::Border::REPLICATE,
-                                nullptr, 0, 0, DIS_MEM_HOST, nullptr, device);
+                if (homography)
+                    dis::warpHomography(src.data(), C, corr.data() + (size_t)t0 * 8, n, W, H, dst.data(),
+                                        dis::Border::REPLICATE, nullptr, 0, 0, DIS_MEM_HOST, nullptr, device);
+                else
+                    dis::warpMotion(src.data(), C, corr.data() + (size_t)t0 * 6, n, W, H, dst.data(), dis::Border::REPLICATE,
+                                    nullptr, 0, 0, DIS_MEM_HOST, nullptr, device);
                 for (int k = 0; k < n; ++k) {
                     const std::string path = "OF_" + frame_name(folder, start + t0 + k) + "_stab.png";
                     if (color)

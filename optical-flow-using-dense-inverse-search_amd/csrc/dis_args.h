@@ -250,6 +250,25 @@ inline const char* check_motion_workspace(int n, int width, int height, size_t* 
     return nullptr;
 }
 
+// dis_flow_fit_homography: dis_flow_fit_motion's chunks, blocks and size rules
+// with 27 sums a chunk; its coordinates are scaled by s, the smallest power of
+// two >= max(W, H, 2) / 2 (so |a|, |b| < 1 and every division by s is exact).
+constexpr int kHomographyTerms = 27;
+inline int homography_scale(int width, int height)
+{
+    const int m = width > height ? (width > 2 ? width : 2) : (height > 2 ? height : 2);
+    int s = 1;
+    while (2 * (long long)s < m) s *= 2;
+    return s;
+}
+inline const char* check_homography_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (const char* why = check_dims(n, width, height, kMaxExactSide, kMaxMotionPixels)) return why;
+    if (motion_blocks(n, width, height) < 0) return "n * width * height too large for one launch";
+    *bytes = (size_t)n * ((size_t)motion_chunks(width, height) * kHomographyTerms + kMotionHead) * 8;
+    return nullptr;
+}
+
 // dis_temporal_denoise_u8: a block per 64 x 16 output pixels and image, up to 8
 // neighbours a call (their pointers travel in the kernel's arguments).
 constexpr int kDenoiseMaxNeighbours = 8;
@@ -373,6 +392,29 @@ inline const char* check_stabilize_buffers(uintptr_t pair_params, uintptr_t corr
     const size_t n = (size_t)n_frames;
     const NamedRange r[4] = {{pair_params, pair_params ? (n - 1) * 24 : 0, "pair_params"},
                              {corrections, n * 24, "corrections"},
+                             {status, status ? n : 0, "status"},
+                             {replaced, replaced ? sizeof(int) : 0, "replaced"}};
+    return check_disjoint(r, 1, 4, why);
+}
+
+// dis_warp_homography_u8 and dis_homography_stabilize: their affine siblings'
+// sizes and values (check_warp_motion_sizes, check_stabilize) and the same
+// buffer rules with 32 bytes a model.
+inline const char* check_warp_homography_buffers(uintptr_t src, size_t image_bytes, uintptr_t params, int n,
+                                                 uintptr_t dst, size_t dst_bytes, uintptr_t valid, size_t pixels,
+                                                 size_t params_align, PairMessage* why)
+{
+    if (params_align && (params & (params_align - 1))) return "params must be 4-byte aligned";
+    const NamedRange r[4] = {{src, image_bytes, "src"}, {params, (size_t)32 * (size_t)n, "params"},
+                             {dst, dst_bytes, "dst"}, {valid, valid ? pixels : 0, "valid"}};
+    return check_disjoint(r, 2, 4, why);
+}
+inline const char* check_homography_stabilize_buffers(uintptr_t pair_params, uintptr_t corrections, uintptr_t status,
+                                                      uintptr_t replaced, int n_frames, PairMessage* why)
+{
+    const size_t n = (size_t)n_frames;
+    const NamedRange r[4] = {{pair_params, pair_params ? (n - 1) * 32 : 0, "pair_params"},
+                             {corrections, n * 32, "corrections"},
                              {status, status ? n : 0, "status"},
                              {replaced, replaced ? sizeof(int) : 0, "replaced"}};
     return check_disjoint(r, 1, 4, why);

@@ -385,6 +385,109 @@ dis_status dis_warp_motion_u8(const uint8_t* src, size_t src_stride, size_t src_
                                                           height, zero, ddst, dvalid, s); }, "motion warp");
 }
 
+dis_status dis_flow_fit_homography_workspace(int n, int width, int height, size_t* bytes)
+{
+    if (!bytes) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_homography_workspace(n, width, height, bytes));
+    return DIS_OK;
+}
+
+dis_status dis_flow_fit_homography(const void* flow, int flow_format, const uint8_t* mask, int n, int width, int height,
+                                   int iterations, float threshold, float* params, uint32_t* info, uint8_t* inliers,
+                                   void* workspace, dis_mem where, void* stream, int device)
+{
+    if (!flow || !params) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    size_t ws_bytes = 0;
+    DIS_ARG(dis::check_homography_workspace(n, width, height, &ws_bytes));  // sizes and the grid limit
+    if (bad_format(flow_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "flow_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    if (iterations < 0 || iterations > 16) return fail(DIS_ERR_INVALID_ARGUMENT, "iterations must be in [0, 16]");
+    if (!std::isfinite(threshold) || threshold < 0.0f)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "threshold must be finite and >= 0");
+    const bool dev = where == DIS_MEM_DEVICE;
+    if (dev && !workspace) return fail(DIS_ERR_INVALID_ARGUMENT, "device pointers need a workspace");
+    if (dev && (addr(workspace) & 7)) return fail(DIS_ERR_INVALID_ARGUMENT, "workspace must be 8-byte aligned");
+    const size_t px = (size_t)width * height * n;
+    const size_t fsz = flow_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    // (a null mask, info or inliers and a host call's workspace take no part)
+    const dis::NamedRange r[6] = {{addr(flow), px * fsz, "flow"}, {addr(mask), mask ? px : 0, "mask"},
+                                  {addr(params), sizeof(float) * 8 * n, "params"},
+                                  {addr(info), info ? sizeof(uint32_t) * 4 * n : 0, "info"},
+                                  {addr(inliers), inliers ? px : 0, "inliers"},
+                                  {addr(workspace), dev ? ws_bytes : 0, "workspace"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 2, 6, &why));
+    if (dev && (addr(flow) & (fsz - 1)))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "flow must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16)");
+    if (dev && ((addr(params) | addr(info)) & 3))
+        return fail(DIS_ERR_INVALID_ARGUMENT, "params and info must be 4-byte aligned");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dis::HostStage st(s, !dev);
+    const void* dflow = st.in(flow, px * fsz);
+    const uint8_t* dmask = st.in(mask, px);
+    float* dparams = st.out(params, sizeof(float) * 8 * n);
+    uint32_t* dinfo = st.out(info, sizeof(uint32_t) * 4 * n);
+    uint8_t* dinliers = st.out(inliers, px);
+    void* dws = dev ? workspace : st.scratch(ws_bytes);
+    return st.finish([&] { return dis::launch_fit_homography(dflow, flow_format == DIS_FLOW_F16, dmask, n, width, height,
+                                                             iterations, threshold, dparams, dinfo, dinliers, dws, s); },
+                     "homography fit");
+}
+
+dis_status dis_homography_to_flow(const float* params, int n, int width, int height, void* out, int out_format,
+                                  dis_mem where, void* stream, int device)
+{
+    if (!params || !out) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_motion_flow(n, width, height));
+    if (bad_format(out_format)) return fail(DIS_ERR_INVALID_ARGUMENT, "out_format must be DIS_FLOW_F32 or DIS_FLOW_F16");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    const size_t px = (size_t)width * height * n;
+    const size_t osz = out_format == DIS_FLOW_F16 ? 4 : 8;  // bytes of one (u,v) pair
+    const dis::NamedRange r[2] = {{addr(params), sizeof(float) * 8 * n, "params"}, {addr(out), px * osz, "out"}};
+    dis::PairMessage why;
+    DIS_ARG(dis::check_disjoint(r, 1, 2, &why));
+    if (where == DIS_MEM_DEVICE && ((addr(out) & (osz - 1)) || (addr(params) & 3)))
+        return fail(DIS_ERR_INVALID_ARGUMENT,
+                    "out must be aligned to one (u,v) pair (8 bytes f32, 4 bytes f16), params to 4 bytes");
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dis::HostStage st(s, where == DIS_MEM_HOST);
+    const float* dparams = st.in(params, sizeof(float) * 8 * n);
+    void* dout = st.out(out, px * osz);
+    return st.finish([&] { return dis::launch_homography_flow(dparams, n, width, height, dout, out_format == DIS_FLOW_F16,
+                                                              s); }, "homography field");
+}
+
+dis_status dis_warp_homography_u8(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                                  const float* params, int n, int width, int height, int border, uint8_t* dst,
+                                  uint8_t* valid, dis_mem where, void* stream, int device)
+{
+    if (!src || !params || !dst) return fail(DIS_ERR_INVALID_ARGUMENT, "null pointer");
+    DIS_ARG(dis::check_warp_motion_sizes(n, width, height, channels));  // sizes, channels and the grid
+    if (border != DIS_BORDER_REPLICATE && border != DIS_BORDER_ZERO)
+        return fail(DIS_ERR_INVALID_ARGUMENT, "border must be DIS_BORDER_REPLICATE or DIS_BORDER_ZERO");
+    if (bad_mem(where)) return fail(DIS_ERR_INVALID_ARGUMENT, "bad dis_mem");
+    dis::ImageStack im;
+    DIS_ARG(dis::check_image_stack(width, height, channels, n, src_stride, src_image_stride, &im));
+    const bool dev = where == DIS_MEM_DEVICE;
+    const size_t px = (size_t)width * height * n;
+    dis::PairMessage why;
+    DIS_ARG(dis::check_warp_homography_buffers(addr(src), im.bytes, addr(params), n, addr(dst), px * channels, addr(valid),
+                                               px, dev ? 4 : 0, &why));
+    if (dis_status st = dis::use_device(device)) return st;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int zero = border == DIS_BORDER_ZERO;
+    // a host source is staged as it lies (rows and images keep their strides)
+    dis::HostStage st(s, !dev);
+    const uint8_t* dsrc = st.in(src, im.bytes);
+    const float* dparams = st.in(params, sizeof(float) * 8 * n);
+    uint8_t* ddst = st.out(dst, px * channels);
+    uint8_t* dvalid = st.out(valid, px);
+    return st.finish([&] { return dis::launch_warp_homography(dsrc, im.stride, im.image_stride, channels, dparams, n, width,
+                                                              height, zero, ddst, dvalid, s); }, "homography warp");
+}
+
 dis_status dis_flow_advect_points(const void* flow, int flow_format, int n, int width, int height, const float* points,
                                   int count, float* points_out, uint8_t* status, dis_mem where, void* stream, int device)
 {

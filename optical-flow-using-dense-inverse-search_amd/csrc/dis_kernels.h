@@ -264,6 +264,20 @@ hipError_t launch_warp_motion(const uint8_t* src, size_t src_stride, size_t src_
                               const float* params, int n, int W, int H, int zero_border, uint8_t* dst, uint8_t* valid,
                               hipStream_t s, Timing t = {}, int direct_only = 0, unsigned* routes = nullptr);
 
+// The eight-parameter family (dis_homography.hip): launch_fit_motion's passes
+// with 27 sums and an 8 x 8 solve (dis_flow_fit_homography; workspace:
+// check_homography_workspace's bytes), the fields of n models of eight
+// parameters (dis_homography_to_flow), and launch_warp_motion's direct form with
+// the projective vector (dis_warp_homography_u8). Pointers, strides and limits
+// as for their affine siblings above.
+hipError_t launch_fit_homography(const void* flow, int f16, const uint8_t* mask, int n, int W, int H, int iterations,
+                                 float threshold, float* params, unsigned* info, uint8_t* inliers, void* workspace,
+                                 hipStream_t s);
+hipError_t launch_homography_flow(const float* params, int n, int W, int H, void* out, int out_f16, hipStream_t s);
+hipError_t launch_warp_homography(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
+                                  const float* params, int n, int W, int H, int zero_border, uint8_t* dst,
+                                  uint8_t* valid, hipStream_t s);
+
 // Motion-compensated temporal denoising of n W x H u8 images of `channels`
 // (1, 3, 4) interleaved samples (dis_denoise.hip, dis_temporal_denoise_u8): one
 // launch, a block per 64 x 16 pixels. `neighbours`, `flows` and `masks` are host

@@ -122,6 +122,8 @@ EXPORTED_SYMBOLS = (
     "dis_denoise_weights", "dis_temporal_denoise_u8",
     "dis_motion_stabilize", "dis_warp_motion_u8",
     "dis_yuv420_to_frames_u8", "dis_frames_to_yuv420_u8",
+    "dis_flow_fit_homography_workspace", "dis_flow_fit_homography", "dis_homography_to_flow",
+    "dis_warp_homography_u8", "dis_homography_stabilize",
 )
 
 
@@ -265,6 +267,12 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "dis_warp_motion_u8"):  # (added within v8)
             L.dis_motion_stabilize.argtypes = [V, I, I, I, I, ctypes.c_float, ctypes.c_float, V, V, P(I)]
             L.dis_warp_motion_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, V, V, I, V, I]
+        if hasattr(L, "dis_flow_fit_homography"):  # (added within v8)
+            L.dis_flow_fit_homography_workspace.argtypes = [I, I, I, P(Z)]
+            L.dis_flow_fit_homography.argtypes = [V, I, V, I, I, I, I, ctypes.c_float, V, V, V, V, I, V, I]
+            L.dis_homography_to_flow.argtypes = [V, I, I, I, V, I, I, V, I]
+            L.dis_homography_stabilize.argtypes = [V, I, I, I, I, ctypes.c_float, ctypes.c_float, V, V, P(I)]
+            L.dis_warp_homography_u8.argtypes = [V, Z, Z, I, V, I, I, I, I, V, V, I, V, I]
         if hasattr(L, "dis_yuv420_to_frames_u8"):  # (added within v8)
             L.dis_yuv420_to_frames_u8.argtypes = [V, Z, Z, V, V, Z, Z, I, I, I, I, I, I, V, Z, Z, I, I, I, V, I]
             L.dis_frames_to_yuv420_u8.argtypes = [V, Z, Z, I, I, I, I, I, I, V, Z, Z, V, V, Z, Z, I, I, V, I]
@@ -813,6 +821,177 @@ def warp_motion_device(src_ptr: int, params_ptr: int, n: int, width: int, height
     bd = _border(border)
     _check(lib().dis_warp_motion_u8(src_ptr, src_stride, src_image_stride, channels, params_ptr, n, width, height, bd,
                                     dst_ptr, valid_ptr or None, MEM_DEVICE, stream or None, device))
+
+
+def _fit_args(iterations, threshold):
+    """(iterations, threshold) of fit_homography, checked as the library checks them."""
+    _, its, thr = _motion_args(MOTION_AFFINE, iterations, threshold)
+    return its, thr
+
+
+def _models8(params, name="params"):
+    """float32 (8,) or (n, 8) models, contiguous."""
+    p = np.asarray(params)
+    if p.dtype != np.float32:
+        raise ValueError(f"{name} dtype must be float32, not {p.dtype}")
+    if p.ndim not in (1, 2) or p.shape[-1] != 8 or p.size == 0:
+        raise ValueError(f"{name} must be (8,) or (n, 8), not {p.shape}")
+    return np.ascontiguousarray(p)
+
+
+def _sides(width, height):
+    if isinstance(width, bool) or isinstance(height, bool) or not isinstance(width, (int, np.integer)) or \
+            not isinstance(height, (int, np.integer)) or width < 1 or height < 1:
+        raise ValueError(f"width and height must be integers >= 1, not {width!r}, {height!r}")
+    return int(width), int(height)
+
+
+def fit_homography_workspace(n: int, width: int, height: int) -> int:
+    """Bytes of device workspace dis_flow_fit_homography needs for n W x H fields
+    on device pointers: n * (ceil(W * H / 16384) * 27 + 16) * 8."""
+    b = ctypes.c_size_t(0)
+    _check(lib().dis_flow_fit_homography_workspace(n, width, height, ctypes.byref(b)))
+    return int(b.value)
+
+
+def fit_homography(flow: np.ndarray, mask=None, iterations: int = 3, threshold: float = 1.0,
+                   return_info: bool = False, return_inliers: bool = False, device: int = 0):
+    """The global motion of flow fields as a homography (dis_flow_fit_homography)
+    on the GPU: what fit_motion does for its three models, for the eight-
+    parameter projective model that a rotating camera induces. flow, mask,
+    iterations, threshold, return_info and return_inliers as for fit_motion.
+    Returns float32 params (8,) or (n, 8): with g = p6 x + p7 y,
+    u = (p0 + p1 x + p2 y - x g) / (1 + g), v = (p3 + p4 x + p5 y - y g) / (1 + g)
+    over pixel indices; NaN where the fit failed (fewer than four vectors in
+    general position, or a model whose horizon comes near the frame). Order:
+    params, info, inliers."""
+    fl = np.asarray(flow)
+    fmt = _flow_format(fl.dtype)
+    if fl.ndim not in (3, 4) or fl.shape[-1] != 2:
+        raise ValueError(f"flow must be (H, W, 2) or (n, H, W, 2), not {fl.shape}")
+    m = _byte_plane(mask, fl.shape[:-1], "mask")
+    its, thr = _fit_args(iterations, threshold)
+    H, W = fl.shape[-3], fl.shape[-2]
+    n = fl.shape[0] if fl.ndim == 4 else 1
+    lead = fl.shape[:-3]
+    fl = np.ascontiguousarray(fl)
+    params = np.empty(lead + (8,), np.float32)
+    info = np.empty(lead + (4,), np.uint32) if return_info else None
+    inl = np.empty(fl.shape[:-1], np.uint8) if return_inliers else None
+    _check(lib().dis_flow_fit_homography(_ptr(fl), fmt, None if m is None else _ptr(m), n, W, H, its, thr,
+                                         _ptr(params), _ptr(info) if return_info else None,
+                                         _ptr(inl) if return_inliers else None, None, MEM_HOST, None, device))
+    out = (params,) + ((info,) if return_info else ()) + ((inl,) if return_inliers else ())
+    return out if len(out) > 1 else params
+
+
+def fit_homography_device(flow_ptr: int, flow_dtype, n: int, width: int, height: int, params_ptr: int,
+                          workspace_ptr: int, iterations: int = 3, threshold: float = 1.0, mask_ptr: int = 0,
+                          info_ptr: int = 0, inliers_ptr: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_flow_fit_homography on raw device pointers, asynchronous on `stream`:
+    no allocation and no host synchronisation. workspace_ptr:
+    fit_homography_workspace(n, width, height) bytes, 8-byte aligned; params_ptr:
+    n * 8 float32; info_ptr: n * 4 uint32; inliers_ptr: n * W * H bytes."""
+    fmt = _flow_format(flow_dtype)
+    its, thr = _fit_args(iterations, threshold)
+    _check(lib().dis_flow_fit_homography(flow_ptr, fmt, mask_ptr or None, n, width, height, its, thr, params_ptr,
+                                         info_ptr or None, inliers_ptr or None, workspace_ptr or None, MEM_DEVICE,
+                                         stream or None, device))
+
+
+def homography_to_flow(params: np.ndarray, width: int, height: int, out_dtype=np.float32,
+                       device: int = 0) -> np.ndarray:
+    """The flow field of homographies (dis_homography_to_flow) on the GPU: params
+    float32 (8,) -> (H, W, 2), or (n, 8) -> (n, H, W, 2), as out_dtype (float32
+    or float16). A model with a parameter that is not finite gives a NaN field,
+    a pixel behind the model's horizon (1 + p6 x + p7 y <= 0) a NaN vector; with
+    p6 = p7 = 0 the field is motion_to_flow's of p0..p5 bit for bit."""
+    p = _models8(params)
+    o_fmt = _flow_format(out_dtype)
+    W, H = _sides(width, height)
+    n = p.shape[0] if p.ndim == 2 else 1
+    out = np.empty(p.shape[:-1] + (H, W, 2), _FLOW_DTYPES[o_fmt])
+    _check(lib().dis_homography_to_flow(_ptr(p), n, W, H, _ptr(out), o_fmt, MEM_HOST, None, device))
+    return out
+
+
+def homography_to_flow_device(params_ptr: int, n: int, width: int, height: int, out_ptr: int, out_dtype=np.float32,
+                              stream: int = 0, device: int = 0) -> None:
+    """dis_homography_to_flow on raw device pointers, asynchronous on `stream`."""
+    o_fmt = _flow_format(out_dtype)
+    _check(lib().dis_homography_to_flow(params_ptr, n, width, height, out_ptr, o_fmt, MEM_DEVICE, stream or None,
+                                        device))
+
+
+def stabilize_path_homography(pair_params, width: int, height: int, radius: int, sigma=None, zoom: float = 1.0,
+                              with_status: bool = False):
+    """stabilize_path for homographies (dis_homography_stabilize, host only):
+    float32 (N-1, 8) pair models (fit_homography's params) -> float32 (N, 8)
+    corrections, what warp_homography takes. The path is a product of 3 x 3
+    matrices kept at bottom-right 1 and smoothed entry by entry. Affine inputs
+    (p6 = p7 = 0) give affine corrections. with_status as for stabilize_path."""
+    r, s, z = _stabilize_args(radius, sigma, zoom)
+    p = np.asarray(pair_params)
+    if p.dtype != np.float32:
+        raise ValueError(f"pair_params dtype must be float32, not {p.dtype}")
+    if p.ndim != 2 or p.shape[1] != 8:
+        raise ValueError(f"pair_params must be (N-1, 8), not {p.shape}")
+    W, H = _sides(width, height)
+    p = np.ascontiguousarray(p)
+    n = p.shape[0] + 1
+    out = np.empty((n, 8), np.float32)
+    status = np.empty(n, np.uint8)
+    replaced = ctypes.c_int(0)
+    _check(lib().dis_homography_stabilize(_ptr(p) if n > 1 else None, n, W, H, r, s, z, _ptr(out), _ptr(status),
+                                          ctypes.byref(replaced)))
+    return (out, status, int(replaced.value)) if with_status else out
+
+
+def warp_homography(image: np.ndarray, params: np.ndarray, border="replicate", return_valid: bool = False,
+                    device: int = 0):
+    """Backward warp (dis_warp_homography_u8) of u8 images by homographies on the
+    GPU: bit for bit flow_warp(image, homography_to_flow(params, W, H)), without
+    the field. image: (H, W) or (H, W, C) with params float32 (8,), or (n, H, W)
+    or (n, H, W, C) with params (n, 8); C in 1, 3, 4. border, return_valid and
+    non-finite models as for warp_motion; a pixel behind the horizon gets 0 and
+    valid 0."""
+    bd = _border(border)
+    img = np.asarray(image)
+    if img.dtype != np.uint8:
+        raise ValueError(f"image dtype must be uint8, not {img.dtype}")
+    p = _models8(params)
+    if p.ndim == 1:
+        if img.ndim not in (2, 3):
+            raise ValueError("one model takes an (H, W) or (H, W, C) image")
+        shape4 = (1,) + img.shape + ((1,) if img.ndim == 2 else ())
+    else:
+        if img.ndim not in (3, 4):
+            raise ValueError("(n, 8) models take (n, H, W) or (n, H, W, C) images")
+        shape4 = img.shape + ((1,) if img.ndim == 3 else ())
+        if shape4[0] != p.shape[0]:
+            raise ValueError(f"image shape {img.shape} does not match params shape {p.shape}")
+    n, H, W, C = shape4
+    if C not in (1, 3, 4):
+        raise ValueError(f"image must have 1, 3 or 4 channels, not {C}")
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError(f"image shape {img.shape} has an empty dimension")
+    img = np.ascontiguousarray(img)
+    out = np.empty(img.shape, np.uint8)
+    valid = np.empty(shape4[:3] if p.ndim == 2 else shape4[1:3], np.uint8) if return_valid else None
+    _check(lib().dis_warp_homography_u8(_ptr(img), 0, 0, C, _ptr(p), n, W, H, bd, _ptr(out),
+                                        _ptr(valid) if return_valid else None, MEM_HOST, None, device))
+    return (out, valid) if return_valid else out
+
+
+def warp_homography_device(src_ptr: int, params_ptr: int, n: int, width: int, height: int, channels: int,
+                           dst_ptr: int, valid_ptr: int = 0, border="replicate", src_stride: int = 0,
+                           src_image_stride: int = 0, stream: int = 0, device: int = 0) -> None:
+    """dis_warp_homography_u8 on raw device pointers (params_ptr: n * 8 float32 in
+    device memory), asynchronous on `stream`: one launch, no allocation, no
+    synchronisation."""
+    bd = _border(border)
+    _check(lib().dis_warp_homography_u8(src_ptr, src_stride, src_image_stride, channels, params_ptr, n, width, height,
+                                        bd, dst_ptr, valid_ptr or None, MEM_DEVICE, stream or None, device))
 
 
 DENOISE_MAX_NEIGHBOURS = 8
@@ -1506,6 +1685,45 @@ class DenseInverseSearch:
         dout = torch.empty_like(dfr)
         warp_motion_device(dfr.data_ptr(), dcorr.data_ptr(), N, W, H, C, dout.data_ptr(), border=bd,
                            device=self.device)
+        out = dout.cpu().numpy()
+        return (out, pair, corr) if return_models else out
+
+    def stabilize_homography(self, frames, radius: int = 15, sigma=None, zoom: float = 1.0, iterations: int = 3,
+                             threshold: float = 1.0, border="replicate", return_models: bool = False):
+        """stabilize with the eight-parameter model, for a camera that rotates:
+        the same chain with fit_homography, stabilize_path_homography and
+        warp_homography in the places of fit_motion, stabilize_path and
+        warp_motion. return_models: (frames, pair models (N - 1, 8), corrections
+        (N, 8))."""
+        its, thr = _fit_args(iterations, threshold)  # all raise before any device call
+        _stabilize_args(radius, sigma, zoom)
+        bd = _border(border)
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        fr, _, N, row = self._frames(fr, fr)
+        import torch
+
+        W, H, C = self.width, self.height, self._frame_channels
+        dev = torch.device("cuda", self.device)
+        dfr = torch.from_numpy(fr if fr.flags.writeable else fr.copy()).to(dev)  # (torch wants a writable source)
+        pair = np.empty((N - 1, 8), np.float32)
+        if N > 1:
+            nb = min(self.max_batch, N - 1)
+            dflow = torch.empty((nb, H, W, 2), dtype=torch.float16 if self.flow_dtype == np.float16 else torch.float32,
+                                device=dev)
+            dpar = torch.empty((N - 1, 8), dtype=torch.float32, device=dev)
+            dws = torch.empty(fit_homography_workspace(nb, W, H) // 8, dtype=torch.float64, device=dev)
+            for k in range(0, N - 1, nb):
+                b = min(nb, N - 1 - k)
+                self.calc_device(b, dfr[k].data_ptr(), dfr[k + 1].data_ptr(), dflow.data_ptr(), stride=row,
+                                 pair_stride=row * H)
+                fit_homography_device(dflow.data_ptr(), self.flow_dtype, b, W, H, dpar[k].data_ptr(), dws.data_ptr(),
+                                      iterations=its, threshold=thr, device=self.device)
+            pair = dpar.cpu().numpy()
+        corr = stabilize_path_homography(pair, W, H, radius, sigma, zoom)
+        dcorr = torch.from_numpy(corr).to(dev)
+        dout = torch.empty_like(dfr)
+        warp_homography_device(dfr.data_ptr(), dcorr.data_ptr(), N, W, H, C, dout.data_ptr(), border=bd,
+                               device=self.device)
         out = dout.cpu().numpy()
         return (out, pair, corr) if return_models else out
 
