@@ -508,7 +508,9 @@ dis_status dis_kernel_time(dis_ctx* ctx, int kernel, int* launches, double* tota
  * maxmotion > 0 fixes the motion range; <= 0 uses max(1, max |u| over valid
  * pixels) per field, as the reference's default -1. Invalid vectors (NaN or
  * |component| >= 1e9) are black. Host pointers: synchronous; device pointers:
- * asynchronous on `stream`. Runs on HIP device `device`. */
+ * asynchronous on `stream`. Runs on HIP device `device`. Any n >= 1 runs: the
+ * field index travels in the launch grid's y extent, and a call with more than
+ * 65,535 fields goes out in launches of at most that many. */
 dis_status dis_flow_color(const float* flow, int n, int width, int height, float maxmotion, uint8_t* bgr,
                           dis_mem where, void* stream, int device);
 

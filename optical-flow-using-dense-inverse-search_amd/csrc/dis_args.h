@@ -156,6 +156,52 @@ inline const char* check_points(int n, int count, size_t* points)
     return nullptr;
 }
 
+// Blocks of the launches whose grid is one-dimensional over all images (256
+// lanes a block); -1 when they exceed a grid, and the entry point refuses the
+// call. Pure, so that tests/cpp can run them: the kernels' files assert the
+// lane counts they assume.
+constexpr int kFlatThreads = 256;
+
+// dis_flow_warp_u8, dis_flow_consistency, dis_flow_compose and the blend of
+// dis_flow_interp_u8: a lane per 4 pixels of a row, n * H rows.
+inline long long row_quad_blocks(int n, int W, int H)
+{
+    const long long rows = (long long)n * H, cw = (W + 3) / 4;
+    if (rows > 0x7fffffffLL * kFlatThreads / cw) return -1;
+    return (rows * cw + kFlatThreads - 1) / kFlatThreads;
+}
+inline long long flow_warp_blocks(int n, int W, int H) { return row_quad_blocks(n, W, H); }
+inline long long flow_consistency_blocks(int n, int W, int H) { return row_quad_blocks(n, W, H); }
+inline long long flow_compose_blocks(int n, int W, int H) { return row_quad_blocks(n, W, H); }
+
+// dis_flow_advect_points: a lane per point.
+inline long long flow_advect_blocks(int n, int count)
+{
+    const long long items = (long long)n * count;
+    if (items > 0x7fffffffLL * kFlatThreads) return -1;
+    return (items + kFlatThreads - 1) / kFlatThreads;
+}
+
+// The splat of dis_flow_interp_u8: a lane per pixel (the blend's grid is
+// smaller); -1 also when W * H exceeds 2^31.
+inline long long flow_interp_blocks(int n, int W, int H)
+{
+    const long long wh = (long long)W * H;
+    if (wh > (1ll << 31) || n > 0x7fffffffLL * kFlatThreads / wh) return -1;
+    return (wh * n + kFlatThreads - 1) / kFlatThreads;
+}
+
+// dis_frames_to_gray_u8 (and the front stage of a colour context, which takes
+// two stacks): a lane per 16 pixels of a row.
+constexpr int kLumaGroupPixels = 16;
+inline long long frames_to_gray_blocks(long long images, int W, int H)
+{
+    if (images < 1 || W < 1 || H < 1) return -1;
+    const long long cw = ((long long)W + kLumaGroupPixels - 1) / kLumaGroupPixels;
+    if (images > 0x7fffffffLL * kFlatThreads / cw / H) return -1;
+    return (images * H * cw + kFlatThreads - 1) / kFlatThreads;
+}
+
 // The levels of dis_flow_fill's push-pull: level 0 is the W x H field, each
 // further level halves both sides (rounding up) until 1 x 1 at level L. The
 // workspace holds levels 1..L of every field, 8 bytes a cell: off[l] cells lie

@@ -109,6 +109,11 @@ constexpr int kMaxStride = 32;  // per field: [0] max radius bits (one 128-B lin
 constexpr int kThreads = 256;
 constexpr int kBG = 4;               // colour item: kBG groups of 4 consecutive pixels per lane
 constexpr int kBpx = kThreads * 4 * kBG;  // pixels per colour item
+// The field index is gridDim.y. An MI355X reports maxGridSize = {2^31 - 1, 65,536,
+// 65,536}; 65,535 is the y extent every HIP device documents, so a launch takes at
+// most that many fields (within either figure) and a call with more goes out in
+// slices (dis_flow_color's checks put no limit on n of their own).
+constexpr int kMaxFieldsPerLaunch = 65535;
 
 // u / m correctly rounded for a per-field divisor m given rm = RN(1/m)
 // (div_pre, dis_device.h), on the domain where its remainders cannot
@@ -293,11 +298,14 @@ hipError_t launch_flow_color(const float* flow, int n, int W, int H, float maxmo
     a.maxmotion = maxmotion;
     a.vec = a.npix % 4 == 0 && (reinterpret_cast<uintptr_t>(bgr) & 3) == 0 && (reinterpret_cast<uintptr_t>(flow) & 15) == 0;
     const unsigned bx = (unsigned)((a.npix + kBpx - 1) / kBpx);
-    if (maxmotion > 0.0f) {  // fixed range: one colour pass over every field
-        a.flow = reinterpret_cast<const float2*>(flow);
-        a.bgr = bgr;
+    if (maxmotion > 0.0f) {  // fixed range: one colour pass over every field (a launch per kMaxFieldsPerLaunch)
         a.ws = ws;
-        hipLaunchKernelGGL(k_color_px, dim3(bx, n), dim3(kThreads), 0, s, a);
+        for (int f0 = 0; f0 < n; f0 += kMaxFieldsPerLaunch) {
+            a.flow = reinterpret_cast<const float2*>(flow) + (size_t)f0 * a.npix;
+            a.bgr = bgr + (size_t)f0 * a.npix * 3;
+            hipLaunchKernelGGL(k_color_px, dim3(bx, (unsigned)std::min(kMaxFieldsPerLaunch, n - f0)), dim3(kThreads), 0,
+                               s, a);
+        }
         return hipGetLastError();
     }
     hipError_t e = hipMemsetAsync(ws, 0, sizeof(unsigned int) * kMaxStride * (size_t)n, s);
@@ -306,7 +314,9 @@ hipError_t launch_flow_color(const float* flow, int n, int W, int H, float maxmo
     const long long fbytes = a.npix * 8;
     // (r04 A/B, 32 x 1080p fields: 32 / 64 / 128 MB chunks 0.41 / 0.36-0.38 / 0.32-0.34 ms)
     constexpr long long kChunkBytes = 128LL << 20;
-    const int chunk = (int)std::max<long long>(1, std::min<long long>(n, kChunkBytes / std::max(1LL, fbytes)));
+    // (small fields: no more of them than a launch's y extent holds)
+    const int chunk = (int)std::max<long long>(
+        1, std::min<long long>({(long long)n, kChunkBytes / std::max(1LL, fbytes), (long long)kMaxFieldsPerLaunch}));
     const unsigned mb = (unsigned)std::min<long long>(256, (a.npix + 2LL * kThreads * 8 - 1) / (2LL * kThreads * 8));
     auto chunk_args = [&](int f0) {
         ColorArgs c = a;

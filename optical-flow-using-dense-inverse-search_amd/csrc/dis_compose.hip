@@ -226,14 +226,8 @@ void launch_compose_ab(const ComposeArgs& a, bool out16, unsigned grid, hipStrea
 
 }  // namespace
 
-// Blocks of the launch for n W x H fields (a lane per 4 pixels of a row); -1
-// when they exceed the grid limit (the runtime refuses the call).
-long long flow_compose_blocks(int n, int W, int H)
-{
-    const long long rows = (long long)n * H, cw = (W + 3) / 4;
-    if (rows > 0x7fffffffLL * kComposeThreads / cw) return -1;
-    return (rows * cw + kComposeThreads - 1) / kComposeThreads;
-}
+static_assert(kComposeThreads == kFlatThreads && kAdvectThreads == kFlatThreads,
+              "flow_compose_blocks and flow_advect_blocks (dis_args.h) count blocks of 256 lanes");
 
 hipError_t launch_flow_compose(const void* a, int a_f16, const void* b, int b_f16, int n, int W, int H,
                                const uint8_t* valid_a, const uint8_t* mask_b, void* out, int out_f16,
@@ -268,15 +262,6 @@ hipError_t launch_flow_compose(const void* a, int a_f16, const void* b, int b_f1
     else
         launch_compose_ab<LoadF32, LoadF32>(g, out_f16 != 0, grid, s, t);
     return hipGetLastError();
-}
-
-// Blocks of the launch for n fields of `count` points (a lane per point); -1
-// when they exceed the grid limit.
-long long flow_advect_blocks(int n, int count)
-{
-    const long long items = (long long)n * count;
-    if (items > 0x7fffffffLL * kAdvectThreads) return -1;
-    return (items + kAdvectThreads - 1) / kAdvectThreads;
 }
 
 hipError_t launch_flow_advect(const void* flow, int f16, int n, int W, int H, const float* points, int count,

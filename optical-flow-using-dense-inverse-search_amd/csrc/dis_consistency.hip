@@ -116,14 +116,7 @@ __global__ void __launch_bounds__(kFbThreads) k_fb_check(FbArgs a)
 
 }  // namespace
 
-// Lanes of work of n W x H fields (4 pixels of a row each) and the blocks that
-// hold them; -1 when they exceed the grid limit (the runtime refuses the call).
-long long flow_consistency_blocks(int n, int W, int H)
-{
-    const long long rows = (long long)n * H, cw = (W + 3) / 4;
-    if (rows > 0x7fffffffLL * kFbThreads / cw) return -1;
-    return (rows * cw + kFbThreads - 1) / kFbThreads;
-}
+static_assert(kFbThreads == kFlatThreads, "flow_consistency_blocks (dis_args.h) counts blocks of 256 lanes");
 
 hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int W, int H, float alpha1,
                                    float alpha2, uint8_t* mask, float* err, hipStream_t s, Timing t)

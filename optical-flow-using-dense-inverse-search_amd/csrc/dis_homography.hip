@@ -214,7 +214,8 @@ __device__ __forceinline__ bool fit_homography(const double* S, double* c)
 __global__ void __launch_bounds__(kSolveThreads) k_homography_solve(HomographySolveArgs h)
 {
     __shared__ double S[kHT];
-    const int f = blockIdx.x, t = threadIdx.x;
+    const long long f = blockIdx.x;  // (f * 8 passes 2^31 from 268,435,456 fields on)
+    const int t = threadIdx.x;
     double* const head = h.ws + f * h.ws_field;
     if (t < kHT) {  // the chunks in turn; eight loads in flight
         const double* const p = head + kMotionHead + t;
@@ -299,7 +300,7 @@ __global__ void __launch_bounds__(kMotionThreads) k_homography_inliers(Homograph
     if (!h.info) return;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) count += __shfl_xor(count, o, 64);
-    if ((lane & 63) == 0 && count) atomicAdd(h.info + f * 4 + 3, count);
+    if ((lane & 63) == 0 && count) atomicAdd(h.info + (long long)f * 4 + 3, count);
 }
 
 // The vector of eight parameters at pixel (x, y); false where d is not > 0 (the

@@ -248,21 +248,11 @@ void launch_interp_c(const InterpArgs& a, bool f16, unsigned grid, hipStream_t s
 
 }  // namespace
 
-// Blocks of the splat for n W x H pairs (a lane per pixel; the blend's grid is
-// smaller); -1 when W * H exceeds 2^31 or the blocks the grid limit (the
-// runtime refuses the call).
-long long flow_interp_blocks(int n, int W, int H)
-{
-    const long long wh = (long long)W * H;
-    if (wh > (1ll << 31) || n > 0x7fffffffLL * kInterpThreads / wh) return -1;
-    return (wh * n + kInterpThreads - 1) / kInterpThreads;
-}
-
 hipError_t launch_flow_interp(const uint8_t* I0, const uint8_t* I1, size_t stride, size_t image_stride, int channels,
                               const void* fw, const void* bw, int f16, int n, int W, int H, float t, uint8_t* dst,
                               uint8_t* fill, void* workspace, hipStream_t s, Timing t_splat, Timing t_blend)
 {
-    static_assert(kInterpThreads == 256, "flow_warp_blocks counts blocks of 256 lanes");
+    static_assert(kInterpThreads == kFlatThreads, "flow_warp_blocks and flow_interp_blocks (dis_args.h) count blocks of 256 lanes");
     const long long blocks = flow_warp_blocks(n, W, H);  // the blend: a lane per 4 pixels of a row, as the warp
     const long long wh = (long long)W * H;
     if (blocks < 1 || flow_interp_blocks(n, W, H) < 1 || wh > (1ll << 31) || (channels != 1 && channels != 3 && channels != 4)) return hipErrorInvalidValue;

@@ -3,6 +3,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "dis_args.h"  // the launches' block counts (flow_warp_blocks, ...)
 #include "dis_common.h"
 
 namespace dis {
@@ -177,7 +178,6 @@ size_t flow_color_ws_words(int n);
 // Forward-backward consistency of n W x H (u,v) fields (dis_consistency.hip):
 // mask (u8, 255 = consistent) and, if err is non-null, the squared round-trip
 // distance per pixel. fw and bw 8-byte aligned.
-long long flow_consistency_blocks(int n, int W, int H);  // grid size of the launch
 hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int W, int H, float alpha1,
                                    float alpha2, uint8_t* mask, float* err, hipStream_t s, Timing t = {});
 
@@ -186,7 +186,6 @@ hipError_t launch_flow_consistency(const float* fw, const float* bw, int n, int 
 // at (x + scale * u, y + scale * v); valid (u8, 255 = target inside the frame)
 // may be null. f16 != 0: `flow` holds __half2 vectors (4-byte aligned), else
 // float2 (8-byte aligned). Strides in bytes, already resolved (never 0).
-long long flow_warp_blocks(int n, int W, int H);  // grid size of the launch
 hipError_t launch_flow_warp(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
                             const void* flow, int f16, int n, int W, int H, float scale, int zero_border,
                             uint8_t* dst, uint8_t* valid, hipStream_t s, Timing t = {});
@@ -200,7 +199,6 @@ hipError_t launch_flow_warp(const uint8_t* src, size_t src_stride, size_t src_im
 // fill (u8, 0 / 1 / 2) may be null. flow_interp_blocks(n, W, H) >= 1: the
 // splat's grid (a lane per pixel), -1 when W * H > 2^31 or the grid limit is
 // exceeded.
-long long flow_interp_blocks(int n, int W, int H);
 hipError_t launch_flow_interp(const uint8_t* I0, const uint8_t* I1, size_t stride, size_t image_stride, int channels,
                               const void* fw, const void* bw, int f16, int n, int W, int H, float t, uint8_t* dst,
                               uint8_t* fill, void* workspace, hipStream_t s, Timing t_splat = {}, Timing t_blend = {});
@@ -211,14 +209,12 @@ hipError_t launch_flow_interp(const uint8_t* I0, const uint8_t* I1, size_t strid
 // taps of b / mask_b is not to be trusted. *_f16 != 0: that field holds __half2
 // vectors (4-byte aligned), else float2 (8-byte aligned). valid_a, mask_b and
 // valid_out may be null; out may be a (equal formats) and valid_out valid_a.
-long long flow_compose_blocks(int n, int W, int H);  // grid size of the launch
 hipError_t launch_flow_compose(const void* a, int a_f16, const void* b, int b_f16, int n, int W, int H,
                                const uint8_t* valid_a, const uint8_t* mask_b, void* out, int out_f16,
                                uint8_t* valid_out, hipStream_t s, Timing t = {});
 // n fields, `count` (x, y) float pairs each, moved by the field sampled at them
 // (dis_flow_advect_points); points 8-byte aligned, status (u8) may be null,
 // points_out may be points.
-long long flow_advect_blocks(int n, int count);  // grid size of the launch
 hipError_t launch_flow_advect(const void* flow, int f16, int n, int W, int H, const float* points, int count,
                               float* points_out, uint8_t* status, hipStream_t s, Timing t = {});
 
@@ -314,7 +310,6 @@ hipError_t launch_flow_convert(const void* src, int src_format, void* dst, size_
 // unknown format. frames_to_gray_blocks: the launch's grid for `images` images,
 // -1 when it exceeds the grid limit.
 int frame_format_channels(int format);
-long long frames_to_gray_blocks(long long images, int W, int H);
 hipError_t launch_frames_to_gray(const uint8_t* src0, const uint8_t* src1, size_t src_stride, size_t src_image_stride,
                                  int format, int n, int W, int H, uint8_t* dst0, uint8_t* dst1, size_t dst_stride,
                                  size_t dst_image_stride, hipStream_t s, Timing t = {});

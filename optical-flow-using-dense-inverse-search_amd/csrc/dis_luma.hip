@@ -126,15 +126,8 @@ int frame_format_channels(int format)
     }
 }
 
-// Blocks of the launch for `images` W x H images (a lane per 16 pixels of a
-// row); -1 when they exceed the grid limit (the runtime refuses the call).
-long long frames_to_gray_blocks(long long images, int W, int H)
-{
-    if (images < 1 || W < 1 || H < 1) return -1;
-    const long long cw = ((long long)W + kLumaGroup - 1) / kLumaGroup;
-    if (images > 0x7fffffffLL * kLumaThreads / cw / H) return -1;
-    return (images * H * cw + kLumaThreads - 1) / kLumaThreads;
-}
+static_assert(kLumaThreads == kFlatThreads && kLumaGroup == kLumaGroupPixels,
+              "frames_to_gray_blocks (dis_args.h) counts blocks of 256 lanes of 16 pixels");
 
 hipError_t launch_frames_to_gray(const uint8_t* src0, const uint8_t* src1, size_t src_stride, size_t src_image_stride,
                                  int format, int n, int W, int H, uint8_t* dst0, uint8_t* dst1, size_t dst_stride,

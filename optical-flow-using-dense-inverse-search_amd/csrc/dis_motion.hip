@@ -184,7 +184,8 @@ template <int MODEL>
 __global__ void __launch_bounds__(kSolveThreads) k_motion_solve(MotionSolveArgs a)
 {
     __shared__ double S[kMotionTerms];
-    const int f = blockIdx.x, t = threadIdx.x;
+    const long long f = blockIdx.x;  // (f * 6 passes 2^31 from 357,913,942 fields on)
+    const int t = threadIdx.x;
     double* const head = a.ws + f * a.ws_field;
     if (t < kMotionTerms) {  // the chunks in turn; eight loads in flight
         const double* const p = head + kMotionHead + t;
@@ -247,7 +248,7 @@ __global__ void __launch_bounds__(kMotionThreads) k_motion_inliers(MotionArgs a)
     if (!a.info) return;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) count += __shfl_xor(count, o, 64);
-    if ((lane & 63) == 0 && count) atomicAdd(a.info + f * 4 + 3, count);
+    if ((lane & 63) == 0 && count) atomicAdd(a.info + (long long)f * 4 + 3, count);
 }
 
 struct MotionFlowArgs {

@@ -137,14 +137,7 @@ void launch_warp_c(const WarpArgs& a, bool f16, unsigned grid, hipStream_t s, Ti
 
 }  // namespace
 
-// Blocks of the launch for n W x H images (a lane per 4 pixels of a row); -1
-// when they exceed the grid limit (the runtime refuses the call).
-long long flow_warp_blocks(int n, int W, int H)
-{
-    const long long rows = (long long)n * H, cw = (W + 3) / 4;
-    if (rows > 0x7fffffffLL * kWarpThreads / cw) return -1;
-    return (rows * cw + kWarpThreads - 1) / kWarpThreads;
-}
+static_assert(kWarpThreads == kFlatThreads, "flow_warp_blocks (dis_args.h) counts blocks of 256 lanes");
 
 hipError_t launch_flow_warp(const uint8_t* src, size_t src_stride, size_t src_image_stride, int channels,
                             const void* flow, int f16, int n, int W, int H, float scale, int zero_border,

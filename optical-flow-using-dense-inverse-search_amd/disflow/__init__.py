@@ -337,6 +337,13 @@ def flow_color(flow: np.ndarray, maxmotion: float = -1.0, device: int = 0) -> np
     return out[0] if single else out
 
 
+def flow_color_device(flow_ptr: int, n: int, width: int, height: int, bgr_ptr: int, maxmotion: float = -1.0,
+                      stream: int = 0, device: int = 0) -> None:
+    """dis_flow_color on raw device pointers (float32 fields, n * W * H * 3 bytes of BGR),
+    asynchronous on `stream`."""
+    _check(lib().dis_flow_color(flow_ptr, n, width, height, float(maxmotion), bgr_ptr, MEM_DEVICE, stream or None, device))
+
+
 def flow_consistency(fw: np.ndarray, bw: np.ndarray, alpha1: float = 0.01, alpha2: float = 0.5,
                      with_err: bool = False, device: int = 0):
     """Forward-backward consistency (dis_flow_consistency) of (H, W, 2) or

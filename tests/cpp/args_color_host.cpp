@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -81,6 +82,7 @@ int main()
         expect(dis::check_init_aliasing(I0 + 3072, 64, 0x900000, 4096, I0, 0x500000, 3072) == nullptr,
                "the same init after a gray frame");
     }
+    far::color(&failures);  // dis_flow_color with more fields than a launch's y extent (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -186,6 +187,7 @@ int main()
         expect(dis::check_points(0, 5, &pts) && dis::check_points(5, 0, &pts) && dis::check_points(-1, 5, &pts) &&
                    dis::check_points(5, -1, &pts), "n or count < 1");
     }
+    far::compose(&failures);  // the far cases (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

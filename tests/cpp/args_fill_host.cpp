@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -199,6 +200,7 @@ int main()
         c.level = top - 50;
         expect(rule(c) != nullptr, "level inside the workspace at the top");
     }
+    far::fill(&failures);  // the far cases (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

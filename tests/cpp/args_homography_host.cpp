@@ -19,6 +19,7 @@
 
 #include "dis_abi.h"
 #include "dis_args.h"
+#include "far_cases.h"
 
 namespace dis {
 static std::string g_error;
@@ -185,6 +186,8 @@ int main()
                    dis_homography_stabilize(pair.data(), 2, W, H, 1, 1.0f, 0.5f, out.data(), nullptr, nullptr) == DIS_ERR_INVALID_ARGUMENT,
                "radius, sigma, zoom");
     }
+    far::motion(27, &failures);  // the far cases (far_cases.h; dis_warp_homography_u8's sizes are dis_warp_motion_u8's rule,
+                                  // which args_stabilize_host runs at them)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

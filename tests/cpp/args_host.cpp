@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -278,6 +279,7 @@ int main()
     image_stacks();
     frame_batches();
     disjointness();
+    far::flat_families(&failures);  // the far cases of warp, interp, consistency and frames-to-gray (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -142,6 +143,7 @@ int main()
         c.params = UINTPTR_MAX - 47;
         expect(rule(c) != nullptr, "no wrap at the top of the address space");
     }
+    far::motion(12, &failures);  // the far cases (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

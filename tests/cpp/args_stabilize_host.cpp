@@ -18,6 +18,7 @@
 
 #include "dis_abi.h"
 #include "dis_args.h"
+#include "far_cases.h"
 
 namespace dis {
 static std::string g_error;
@@ -178,6 +179,7 @@ int main()
         expect(dis_motion_stabilize(pair.data(), 0, W, H, 1, 1.0f, 1.0f, out.data(), nullptr, nullptr) == DIS_ERR_INVALID_ARGUMENT,
                "no frames");
     }
+    far::warp_model(&failures);  // the far cases of dis_warp_motion_u8 (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

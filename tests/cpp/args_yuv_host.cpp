@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dis_args.h"
+#include "far_cases.h"
 
 static int failures = 0;
 
@@ -174,6 +175,7 @@ int main()
                    check_plane_stacks(r, 0, 3, 2, &why) == nullptr,
                "absent chroma (a gray target)");
     }
+    far::yuv(&failures);  // the far cases (far_cases.h)
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

@@ -16,7 +16,7 @@ luma_check: luma_check.cpp $(CLI)/png.hpp
 # any finding aborts: compiled and run (args_color_host.cpp has its own main).
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -O1
 ARGS_OUT ?= args_color_host
-args_color: args_color_host.cpp $(CSRC)/dis_args.h
+args_color: args_color_host.cpp far_cases.h $(CSRC)/dis_args.h
 	g++ $(SAN) -std=c++17 -Wall -I$(CSRC) args_color_host.cpp -o $(ARGS_OUT)
 	ASAN_OPTIONS=detect_leaks=0 $(abspath $(ARGS_OUT))
 

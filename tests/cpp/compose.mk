@@ -8,7 +8,7 @@ CSRC := $(ROOT)/optical-flow-using-dense-inverse-search_amd/csrc
 # run (args_compose_host.cpp has its own main).
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -O1
 ARGS_OUT ?= args_compose_host
-args_compose: args_compose_host.cpp $(CSRC)/dis_args.h
+args_compose: args_compose_host.cpp far_cases.h $(CSRC)/dis_args.h
 	g++ $(SAN) -std=c++17 -Wall -I$(CSRC) args_compose_host.cpp -o $(ARGS_OUT)
 	ASAN_OPTIONS=detect_leaks=0 $(abspath $(ARGS_OUT))
 

@@ -11,7 +11,7 @@ CSRC := $(ROOT)/optical-flow-using-dense-inverse-search_amd/csrc
 # finding aborts: compiled and run (args_stabilize_host.cpp has its own main).
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -O1
 ARGS_OUT ?= args_stabilize_host
-args_stabilize: args_stabilize_host.cpp $(CSRC)/dis_stabilize.cpp $(CSRC)/dis_args.h $(ROOT)/include/dis_abi.h
+args_stabilize: args_stabilize_host.cpp far_cases.h $(CSRC)/dis_stabilize.cpp $(CSRC)/dis_args.h $(ROOT)/include/dis_abi.h
 	g++ $(SAN) -std=c++17 -Wall -ffp-contract=off -I$(ROOT)/include -I$(CSRC) args_stabilize_host.cpp \
 	    $(CSRC)/dis_stabilize.cpp -o $(ARGS_OUT)
 	ASAN_OPTIONS=detect_leaks=0 $(abspath $(ARGS_OUT))

@@ -8,7 +8,7 @@ CSRC := $(ROOT)/optical-flow-using-dense-inverse-search_amd/csrc
 # (args_yuv_host.cpp has its own main).
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -O1
 ARGS_OUT ?= args_yuv_host
-args_yuv: args_yuv_host.cpp $(CSRC)/dis_args.h
+args_yuv: args_yuv_host.cpp far_cases.h $(CSRC)/dis_args.h
 	g++ $(SAN) -std=c++17 -Wall -I$(CSRC) args_yuv_host.cpp -o $(ARGS_OUT)
 	ASAN_OPTIONS=detect_leaks=0 $(abspath $(ARGS_OUT))
 
